@@ -2,6 +2,7 @@
 """bench.py -- two-site DMRG sweep time (+ energy / singular-value error) on MI355X: BASELINE.json's metric.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config heis2048|xxz512|hubbard1024|tebd1024] [--chi CHI] [--L L]
+                    [--full] [--dump-outputs DIR]
 
 Default workload (``config["workload"]``): spin-1/2 Heisenberg chain (XXZ, Jxx=Jz=1, hz=0, Sz conserved), L=100, two-site
 DMRG at bond dimension chi=2048 (BASELINE.json's headline configuration; fits one GPU), Lanczos with N_min=N_max=8 (fixed
@@ -15,7 +16,13 @@ The MPS is synthetic in the sense of the contract: there is no checkpoint to loa
 the Neel product state by an (untimed) chi ramp of single sweeps chi = 64, 64, 128, ..., chi/2, followed by W warm-up
 sweeps at the target chi; then exactly K sweeps are timed between barrier + torch.cuda.synchronize() on both sides.
 
-One JSON line on rank 0:
+A plain run stops there: it reports the timed steps (``value``, ``ms_per_step``, the kernel timers of the timed region and the
+energy error against the offline reference's sweep energies, a file lookup) and exits.  ``--full`` adds everything else below:
+the CPU baselines, parity at scale against the numpy oracle, the TEBD parity and, heis2048 on one GPU, the extra legs
+(``extras``).  ``--dump-outputs DIR`` writes what the last timed step computed (``dump_outputs``) so that two builds can be
+compared output for output; the inputs are fixed (Neel state or a seeded random MPS), so they are the same in every run.
+
+One JSON line on rank 0 (with ``--full``):
 * ``roofline`` describes the DOMINANT kernel family of the timed region, the batched block SVD (``tpa_svd_batch``): HIP
   events on the launch stream around every call, algorithmic flops ``4 m^2 n + 8 m n^2 + 9 n^3`` and bytes
   ``8 (mn + mk + kn + k)`` per charge block (SURVEY 8(d)), against the fp64 MFMA peak and (``hbm_frac``) the HBM peak;
@@ -68,6 +75,11 @@ def parse(argv=None):
                     "row-sharded engine, so that the collective of the N > 1 path executes on a one-GPU box (TPA_BENCH_FORCE_DIST=1 does the same)")
     ap.add_argument('--no-extras', action='store_true', help="heis2048 on one GPU: skip the legs after the headline (adaptive Lanczos sweep, "
                     "other BASELINE configurations, TeNPy's own engine on the device, vector-kernel roofline)")
+    ap.add_argument('--full', action='store_true', help="also measure and check what the headline figure does not need: the CPU baselines "
+                    "(TeNPy itself, the numpy port), parity at scale against the oracle, the TEBD parity against the offline reference and, "
+                    "heis2048 on one GPU, the extra legs (narrowed by --no-cpu-baseline / --no-extras)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help="after the timed steps, write what the last one computed "
+                    "(energies, Schmidt values, a fixed seeded sample of the MPS tensors) as DIR/<name>.npy, float64")
     return ap.parse_args(argv)
 
 
@@ -116,7 +128,7 @@ def parity_and_port(eng, args, gpu_bond_s):
         # --- device side of the comparison
         if os.environ.get('TPA_DUMP_THETA') and i0 == bonds[0]:
             # charge blocks of the wave function the SVD sees (after one Lanczos run), for scripts/svd_file_bench.py: this is how
-            # scripts/data/theta_chi2048_sat.npz (not tracked: 25 MB) is produced -- `TPA_DUMP_THETA=path python bench.py`
+            # scripts/data/theta_chi2048_sat.npz (not tracked: 25 MB) is produced -- `TPA_DUMP_THETA=path python bench.py --full`
             _, th_opt, _ = LanczosGroundState(fac, th_fac, {'N_min': args.lanczos_N, 'N_max': args.lanczos_N}).run()
             np.savez(os.environ['TPA_DUMP_THETA'], **{'b%02d' % k: np.asarray(b) for k, b in enumerate(fac.prepare_svd(th_opt)._data)})
         npc.svd_engine_floor = True       # the parity sample measures the SVD as the timed sweeps ran it (the engines' floor + clean-up)
@@ -343,6 +355,60 @@ def random_right_canonical_mps(p, L, chi, dtype, seed):
     return MPS([p] * L, Bs, Ss, form='B')
 
 
+DUMP_SAMPLE_PER_SITE = 8192
+
+
+def _tensor_sample(T, rng, k):
+    """``k`` entries of the block-sparse site tensor T drawn by ``rng`` (all of them when it has fewer): the stored blocks in
+    lexicographic order of their charge indices, each flattened in row-major order, gathered on the device.  float64; complex
+    entries as (real, imag) pairs."""
+    from tenpy_amd.linalg import _device as dev
+    if T.stored_blocks == 0:
+        return np.zeros(0)
+    order = np.lexsort(np.asarray(T._qdata).T[::-1])
+    sizes = np.asarray(T._block_sizes_flat(), dtype=np.int64)[order]
+    offs = np.asarray(T._offsets, dtype=np.int64)[order]
+    ends = np.cumsum(sizes)
+    total = int(ends[-1])
+    idx = np.sort(rng.choice(total, size=min(k, total), replace=False))
+    blk = np.searchsorted(ends, idx, side='right')
+    pos = offs[blk] + idx - (ends[blk] - sizes[blk])
+    assert pos.min() >= 0 and pos.max() < T._arena.numel(), "block layout does not match the arena"
+    vals = np.ascontiguousarray(dev.to_host(dev.take(T._arena, pos)))
+    return vals.view(np.float64) if np.iscomplexobj(vals) else vals.astype(np.float64)
+
+
+def dump_outputs(eng, is_tebd, out_dir, seed=20240601):
+    """``--dump-outputs DIR``: what the timed path handed its caller after the last timed step, one float64 .npy per name.
+
+    * ``schmidt_values``: (L+1, max chi) the Schmidt spectrum of every bond as the MPS stores it, zero-padded;
+    * ``mps_tensors_sample``: ``DUMP_SAMPLE_PER_SITE`` entries of every site tensor (``_tensor_sample``, fixed seed), site after
+      site -- like any MPS tensor, fixed only up to the phase of each singular vector the SVDs chose;
+    * DMRG: ``energy`` (the sweep's ground-state energy), ``bond_energies`` and ``bond_trunc_err`` (the 2(L-2) bond updates
+      of the last sweep, in order); TEBD: ``trunc_err`` (accumulated) and ``norm``.
+    Less than 10 MB at the default sizes."""
+    os.makedirs(out_dir, exist_ok=True)
+    psi = eng.psi
+    L = psi.L
+    S = [np.asarray(s, dtype=np.float64) for s in psi._S]
+    sv = np.zeros((len(S), max(len(s) for s in S)))
+    for i, s in enumerate(S):
+        sv[i, :len(s)] = s
+    rng = np.random.default_rng(seed)
+    res = {"schmidt_values": sv,
+           "mps_tensors_sample": np.concatenate([_tensor_sample(psi.get_B(i, None), rng, DUMP_SAMPLE_PER_SITE) for i in range(L)])}
+    if is_tebd:
+        res["trunc_err"] = np.array([float(eng.trunc_err.eps)])
+        res["norm"] = np.array([float(eng.norm)])
+    else:
+        n_upd = 2 * (L - 2)
+        res["energy"] = np.array([float(eng.sweep_stats['E'][-1])])
+        res["bond_energies"] = np.asarray(eng.update_stats['E_total'][-n_upd:], dtype=np.float64)
+        res["bond_trunc_err"] = np.asarray(eng.update_stats['err'][-n_upd:], dtype=np.float64)
+    for name, a in res.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def run(argv=None, emit=True):
     """One bench line (dict); printed as JSON by rank 0 when ``emit``."""
     args = parse(argv)
@@ -440,6 +506,8 @@ def run(argv=None, emit=True):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     s_per_step = elapsed / max(args.steps, 1)
+    if args.dump_outputs and rank == 0:        # before anything else touches the state (the extra legs sweep on)
+        dump_outputs(eng, is_tebd, args.dump_outputs)
 
     if rank == 0:
         def roof(tm, kernel, extra):
@@ -525,7 +593,7 @@ def run(argv=None, emit=True):
             elif args.qr and args.eig_svd and os.path.exists(eig_ref):       # ... with use_eig_based_svd=True (truncation.py:473; round 6)
                 tref_file, like_for_like = eig_ref, True
             n_done = args.warmup + args.steps
-            if os.path.exists(tref_file) and world == 1:
+            if args.full and os.path.exists(tref_file) and world == 1:
                 with open(tref_file) as f:
                     tref = json.load(f)
                 if tref.get('L') == L and tref.get('chi') == chi:
@@ -581,7 +649,7 @@ def run(argv=None, emit=True):
             out["lanczos_stats"]["note"] = ("timed sweeps only; n_ill_conditioned = results whose norm differed from 1 by more than 1e-5 before the "
                                             "final normalisation (the forced N_min = N_max = %d runs past convergence), n_degenerate = results that "
                                             "cancelled to zero and were replaced by the start vector" % args.lanczos_N)
-            if world == 1:
+            if world == 1 and args.full:
                 upd_t = eng.update_stats['time'][n0:]
                 mid = [t for i, t in zip(eng.update_stats['i0'][n0:], upd_t) if abs(i - L // 2) <= 1]
                 gpu_bond_s = float(np.mean(mid)) if mid else s_per_step / n_upd
@@ -618,7 +686,7 @@ def run(argv=None, emit=True):
                         base["port"] = port
                 if base is not None:
                     out["cpu_baseline"] = base
-        if world == 1 and not args.no_extras and args.config == 'heis2048' and not is_tebd and chi == CONFIGS['heis2048'][1]:
+        if args.full and world == 1 and not args.no_extras and args.config == 'heis2048' and not is_tebd and chi == CONFIGS['heis2048'][1]:
             try:
                 extras(out, eng, args)
             except Exception as e:      # the extra legs must never kill the bench line
@@ -900,7 +968,7 @@ def extras(out, eng, args):
             is_t = name.startswith("tebd")
             # DMRG configurations: the headline's protocol (5 warm-up sweeps at the target chi, then the timed ones); the figure of the
             # 2 + 2 sweep legs of rounds 4 - 6 (sweeps 3 and 4 at the target chi: still a third cold SVD calls) is kept beside it
-            r = run(argv + (["--steps", "2", "--warmup", "1"] if is_t else ["--steps", "3", "--warmup", "5"]) + ["--no-extras", "--cpu-sample-bonds", "1"], emit=False)
+            r = run(argv + (["--steps", "2", "--warmup", "1"] if is_t else ["--steps", "3", "--warmup", "5"]) + ["--full", "--no-extras", "--cpu-sample-bonds", "1"], emit=False)
             o = {k: r[k] for k in keep if k in r}
             if not is_t:
                 tgt = [e["s"] for e in r.get("untimed_sweeps", []) if str(e.get("kind", "")).startswith("warm-up at the target chi")]

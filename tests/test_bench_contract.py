@@ -15,7 +15,7 @@ def test_bench_json_contract(monkeypatch):
     import torch
     monkeypatch.setattr(torch.cuda, 'synchronize', lambda *a, **k: None)
     monkeypatch.setattr(torch.cuda, 'set_device', lambda *a, **k: None)
-    monkeypatch.setattr(sys, 'argv', ['bench.py', '--L', '12', '--chi', '16', '--steps', '2', '--warmup', '1', '--cpu-sample-bonds', '1'])
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--L', '12', '--chi', '16', '--steps', '2', '--warmup', '1', '--cpu-sample-bonds', '1', '--full'])
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
         monkeypatch.delenv(k, raising=False)
     import bench
@@ -53,6 +53,94 @@ def test_bench_json_contract(monkeypatch):
     assert 'svd' in r['kernel'] and r['launches'] > 0
     assert abs(out['E'] - (-5.142090632841)) < 1e-6          # XXZ Jz=1, L=12 ground state energy (exact: -5.1420906328)
     assert out['sv_kept'] > 0 and out['sv_kept_rel_err_over_1e-10'] == 0
+
+
+def _bench_in_process(monkeypatch, argv):
+    import mock_device
+    mock_device.install(monkeypatch)
+    import torch
+    monkeypatch.setattr(torch.cuda, 'synchronize', lambda *a, **k: None)
+    monkeypatch.setattr(torch.cuda, 'set_device', lambda *a, **k: None)
+    monkeypatch.setattr(sys, 'argv', ['bench.py'] + argv)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK'):
+        monkeypatch.delenv(k, raising=False)
+    import bench
+    buf = io.StringIO()
+    with contextlib.redirect_stdout(buf):
+        bench.main()
+    return json.loads([l for l in buf.getvalue().splitlines() if l.strip()][-1])
+
+
+@pytest.mark.parametrize("config", ["heis2048", "tebd1024"])
+def test_bench_plain_run_is_lean(monkeypatch, config):
+    """Without --full the run is set-up, warm-up, the timed steps and the line: no CPU baseline, no parity sample, no extra leg --
+    and the headline fields still mean what they do with --full."""
+    import bench
+
+    def must_not_run(*a, **k):
+        raise AssertionError("a plain run must not do this")
+    for name in ('parity_and_port', 'reference_same_run', 'extras', 'vector_roofline'):
+        monkeypatch.setattr(bench, name, must_not_run)
+    out = _bench_in_process(monkeypatch, ['--config', config, '--L', '12', '--chi', '16', '--steps', '3', '--warmup', '1'])
+    assert out['steps'] == 3 and out['warmup'] == 1 and out['n_gpus'] == 1 and out['higher_is_better'] is False
+    assert out['value'] > 0 and abs(out['ms_per_step'] - 1e3 * out['value']) < 1e-3 * out['ms_per_step']
+    assert 'cpu_baseline' not in out and 'sv_max_rel_err' not in out and 'other_configs' not in out and 'tebd_parity' not in out
+    assert 'roofline' in out and 'roofline_gemm' in out
+    if config == 'heis2048':
+        assert out['unit'] == 's/sweep' and out['dtype'] == 'f64' and 'energy_err' in out
+        assert abs(out['E'] - (-5.142090632841)) < 1e-6
+    else:
+        assert out['unit'] == 's/step' and out['dtype'] == 'c128' and out['S_mid_entropy'] > 0
+
+
+def test_bench_steps_sets_the_timed_steps(monkeypatch):
+    """--steps K runs exactly K timed sweeps after the ramp and the W warm-up sweeps."""
+    import bench
+    sweeps = []
+    real = bench.build_dmrg
+
+    def counting(*a, **k):
+        eng, E = real(*a, **k)
+        sweep = eng.sweep
+        eng.sweep = lambda: sweeps.append(1) or sweep()
+        sweeps.clear()
+        return eng, E
+    monkeypatch.setattr(bench, 'build_dmrg', counting)
+    out = _bench_in_process(monkeypatch, ['--L', '12', '--chi', '16', '--steps', '4', '--warmup', '2'])
+    assert out['steps'] == 4 and len(sweeps) == 4 + 2
+
+
+def test_bench_dump_outputs(monkeypatch, tmp_path):
+    """--dump-outputs DIR: float64 .npy files of what the last timed step computed, the same in two runs with the same arguments
+    (fixed inputs), and consistent with the line."""
+    import numpy as np
+    runs = []
+    for k in range(2):
+        d = tmp_path / ('run%d' % k)
+        out = _bench_in_process(monkeypatch, ['--L', '12', '--chi', '16', '--steps', '2', '--warmup', '1', '--dump-outputs', str(d)])
+        runs.append({p.stem: np.load(p) for p in sorted(d.glob('*.npy'))})
+    a, b = runs
+    assert set(a) == {'energy', 'bond_energies', 'bond_trunc_err', 'schmidt_values', 'mps_tensors_sample'}
+    assert sum(v.nbytes for v in a.values()) < 64 << 20
+    for name in a:
+        assert a[name].dtype == np.float64 and a[name].size > 0, name
+        np.testing.assert_array_equal(a[name], b[name], err_msg=name)
+    assert a['energy'][0] == out['E'] and a['bond_energies'].shape == (2 * (12 - 2),) and a['bond_energies'][-1] == out['E']
+    S = a['schmidt_values']
+    assert S.shape[0] == 13 and S.shape[1] <= 16
+    np.testing.assert_allclose(np.sum(S[1:-1] ** 2, axis=1), 1., rtol=1e-10)
+    assert np.all(np.isfinite(a['mps_tensors_sample'])) and np.any(a['mps_tensors_sample'] != 0)
+
+
+def test_bench_dump_outputs_tebd(monkeypatch, tmp_path):
+    """The TEBD configuration (complex128 tensors) dumps float64 too: complex entries as (real, imag) pairs."""
+    import numpy as np
+    out = _bench_in_process(monkeypatch, ['--config', 'tebd1024', '--L', '12', '--chi', '16', '--steps', '1', '--warmup', '1',
+                                          '--dump-outputs', str(tmp_path)])
+    got = {p.stem: np.load(p) for p in tmp_path.glob('*.npy')}
+    assert set(got) == {'schmidt_values', 'mps_tensors_sample', 'trunc_err', 'norm'}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got['trunc_err'][0] == pytest.approx(out['trunc_err_eps'], rel=1e-5) and got['mps_tensors_sample'].size % 2 == 0
 
 
 def test_compact_line_fits_with_all_extras():
