@@ -118,6 +118,12 @@ int tpa_lanczos_run(int dtype, int64_t n, const int64_t *ops, int n_ops, void *c
  * the tridiagonal matrix), norm_host[0] = |out| (blocking): `_calc_result_full`, krylov_based.py:223-236, in one pass. */
 int tpa_krylov_combine(int dtype, int64_t n, const void *krylov_dev, int N, const double *coeff, void *out_dev,
                        double *red_out_dev, double *scratch_dev, double *norm_host, void *stream);
+/* The same with COMPLEX coefficients (coeff: N pairs re, im on the host; exp(delta h) e_0 of `LanczosEvolution.run`):
+ * out = scale * sum_{k < N} c_k v_k.  The basis is F64 or C128 (`basis_dtype`), `out_dev` is ALWAYS C128 (n elements): a real
+ * basis with complex c_k is the first time step of a real state.  norm_host[0] = |sum_k c_k v_k| BEFORE `scale` (blocking); the
+ * caller normalises with tpa_scal.  red_out_dev: 2 doubles, scratch_dev: TPA_RED_SCRATCH doubles. */
+int tpa_krylov_combine_z(int basis_dtype, int64_t n, const void *krylov_dev, int N, const double *coeff, double scale,
+                         void *out_dev, double *red_out_dev, double *scratch_dev, double *norm_host, void *stream);
 
 /* ---- K8/K9/K10: data movement ---------------------------------------------------------
  * Generic strided N-d block copy (N <= TPA_COPY_MAXDIM), batched.  Replaces

@@ -1,4 +1,4 @@
-"""Device forms of the two callers that TeNPy's own engines construct per bond update, for the module form of the boundary
+"""Device forms of the callers that TeNPy's own engines construct per bond update, for the module form of the boundary
 (``tenpy_amd.install.install(fused=True)``): the engines (``tenpy/algorithms/dmrg.py:529 update_local``,
 ``mps_common.py:516 make_eff_H``) stay the reference's code; only what they instantiate is rebound.
 
@@ -10,6 +10,10 @@
   applied as block-level linear combinations instead of K = 1 GEMMs.  Bonds the device form does not cover (small sectors,
   MPOs with non-scalar blocks, ``H + h.c.`` environments, exact diagonalisation of small bonds) get the reference's own
   class: ``__new__`` dispatches, so the engines see one ``EffectiveH``.
+* ``device_one_site_h(RefOneSiteH)`` / ``device_zero_site_h(RefZeroSiteH)`` -> the same for the operators TDVP constructs after
+  every two-site / one-site update (``tdvp.py:308 one_site_update``, ``:419 zero_site_update``) on top of
+  ``mps_common.OneSiteH`` / ``ZeroSiteH``; ``combine=True``, ``H + h.c.`` environments, MPO blocks that are not single numbers
+  and non-standard labels get the reference's class.
 * ``hinted_mixed_svd(ref_mixed_svd)`` wraps ``TwoSiteDMRGEngine.mixed_svd`` (``dmrg.py:876``) to tell the block SVD which
   bond it decomposes (``np_conserved.svd_hint``), which enables the warm start of ``linalg/_svd_warm.py``.
 """
@@ -21,14 +25,15 @@ import numpy as np
 from ..linalg import np_conserved as npc
 from . import mps_common as dev_mc
 
-__all__ = ['device_two_site_h', 'hinted_mixed_svd']
+__all__ = ['device_two_site_h', 'device_one_site_h', 'device_zero_site_h', 'hinted_mixed_svd']
 
 # Smallest "largest bond sector" for which the device form is used.  Round 3 measurement (module form on the MI355X, Heisenberg
 # L = 100, mixer ramp): with the reference's own class below 64 -- four generic tensordots with transposed copies per matvec,
 # ~20 device calls and ~1 ms of interpreter time each -- a chi <= 256 sweep took 4.4 - 4.9 s against 0.9 - 1.5 s with the
 # device form everywhere, so the threshold is 1 (kept as a knob for A/B runs).
 MIN_SECTOR = 1
-stats = {'device': 0, 'reference': 0}      # bonds handled by the device form / handed back to the reference's class
+stats = {'device': 0, 'reference': 0,      # bonds handled by the device form / handed back to the reference's class (TwoSiteH)
+         'device_one': 0, 'reference_one': 0, 'device_zero': 0, 'reference_zero': 0}      # the same for OneSiteH / ZeroSiteH
 
 
 def device_two_site_h(Ref):
@@ -110,6 +115,78 @@ def device_two_site_h(Ref):
     DeviceTwoSiteH.__name__ = 'TwoSiteH'
     DeviceTwoSiteH.__qualname__ = 'TwoSiteH'
     return DeviceTwoSiteH
+
+
+def _plain_env(env):
+    return not (getattr(env, 'has_hc', False) or getattr(env.H, 'explicit_plus_hc', False))
+
+
+def device_one_site_h(Ref):
+    class DeviceOneSiteH(dev_mc.OneSiteH):
+        __doc__ = "Device form of tenpy.algorithms.mps_common.OneSiteH (see tenpy_amd/algorithms/module_form.py)."
+        _reference_class = Ref
+
+        def __new__(cls, env, i0, combine=False, move_right=True):
+            tensors = cls._device_tensors(env, i0, combine)
+            if tensors is not None:
+                stats['device_one'] += 1
+                self = object.__new__(cls)
+                self._tensors = tensors
+                return self
+            stats['reference_one'] += 1
+            return Ref(env, i0, combine, move_right)          # not an instance of cls: __init__ is skipped
+
+        @staticmethod
+        def _device_tensors(env, i0, combine):
+            """``(LP, W0, RP)`` if the device form covers this site, else ``None``."""
+            if combine or not _plain_env(env):
+                return None
+            LP, W0, RP = env.get_LP(i0), env.H.get_W(i0), env.get_RP(i0)
+            if list(W0.get_leg_labels()) != ['wL', 'wR', 'p', 'p*'] or dev_mc._mpo_entries(W0) is None or not dev_mc._envs_factorable(LP, RP):
+                return None
+            return LP, W0, RP
+
+        def __init__(self, env, i0, combine=False, move_right=True):
+            LP, W0, RP = self.__dict__.pop('_tensors')
+            self.move_right = move_right
+            self._setup(LP, W0, RP, i0, env.H.dtype)
+
+        from_LP_W0_RP = staticmethod(lambda *args, **kwargs: Ref.from_LP_W0_RP(*args, **kwargs))      # (VUMPS: the reference's form)
+
+        def adjoint(self):
+            raise NotImplementedError("DeviceOneSiteH is not used for H + h.c. environments (see _device_ok)")
+
+    DeviceOneSiteH.__name__ = DeviceOneSiteH.__qualname__ = 'OneSiteH'
+    return DeviceOneSiteH
+
+
+def device_zero_site_h(Ref):
+    class DeviceZeroSiteH(dev_mc.ZeroSiteH):
+        __doc__ = "Device form of tenpy.algorithms.mps_common.ZeroSiteH (see tenpy_amd/algorithms/module_form.py)."
+        _reference_class = Ref
+
+        def __new__(cls, env, i0):
+            if _plain_env(env):
+                LP, RP = env.get_LP(i0), env.get_RP(i0 - 1)
+                if dev_mc._envs_factorable(LP, RP):
+                    stats['device_zero'] += 1
+                    self = object.__new__(cls)
+                    self._tensors = (LP, RP)
+                    return self
+            stats['reference_zero'] += 1
+            return Ref(env, i0)
+
+        def __init__(self, env, i0):
+            LP, RP = self.__dict__.pop('_tensors')
+            self._setup(LP, None, RP, i0, env.H.dtype)
+
+        from_LP_RP = staticmethod(lambda *args, **kwargs: Ref.from_LP_RP(*args, **kwargs))
+
+        def adjoint(self):
+            raise NotImplementedError("DeviceZeroSiteH is not used for H + h.c. environments (see _device_ok)")
+
+    DeviceZeroSiteH.__name__ = DeviceZeroSiteH.__qualname__ = 'ZeroSiteH'
+    return DeviceZeroSiteH
 
 
 def hinted_mixed_svd(ref_mixed_svd):

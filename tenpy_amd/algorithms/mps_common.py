@@ -1,4 +1,4 @@
-"""Effective two-site Hamiltonian: the Lanczos matvec of the hot path.
+"""Effective Hamiltonians: the Lanczos matvec of the hot path (``TwoSiteH``; ``OneSiteH`` / ``ZeroSiteH`` of TDVP at the end of the file).
 
 Mirrors ``TwoSiteH`` of ``tenpy/algorithms/mps_common.py`` (:1245; ``matvec`` :1321-1348, ``combine_Heff``
 :1350, ``combine_theta`` :1374, ``update_LP`` :1421, ``update_RP`` :1430) for ``combine=True``:
@@ -22,7 +22,7 @@ import numpy as np
 from ..linalg import _device as dev
 from ..linalg import np_conserved as npc
 
-__all__ = ['TwoSiteH']
+__all__ = ['TwoSiteH', 'OneSiteH', 'ZeroSiteH']
 
 
 FUSED_HEFF = True     # tuning / test hook: False forces the generic tensordot + combine_legs construction
@@ -363,16 +363,21 @@ class MpoApplyPlan:
         return res
 
 
+def _envs_factorable(LP, RP):
+    """LP / RP as the factored forms contract them: the standard labels in an order that needs no transposed copy, MPO bond legs
+    resolved into 1-wide blocks."""
+    lp, rp = list(LP.get_leg_labels()), list(RP.get_leg_labels())
+    return (sorted(lp) == sorted(['vR*', 'wR', 'vR']) and lp.index('vR*') < lp.index('vR') and
+            sorted(rp) == sorted(['wL', 'vL', 'vL*']) and rp.index('vL') < rp.index('vL*') and
+            bool(np.all(LP.get_leg('wR').get_block_sizes() == 1)) and bool(np.all(RP.get_leg('wL').get_block_sizes() == 1)))
+
+
 def factored_matvec_possible(LP, RP, W0, W1):
     """Whether ``LP . theta . (W0 W1) . RP`` can run as GEMM / block linear combination / GEMM on the tensors as they are stored:
     every MPO block a single number, MPO bond legs of the environments resolved into 1-wide blocks, leg orders that need no
     transposed copy.  ``W0`` / ``W1`` with labels ``p`` or ``p0`` / ``p1``."""
-    lp, rp = list(LP.get_leg_labels()), list(RP.get_leg_labels())
     w0, w1 = list(W0.get_leg_labels()), list(W1.get_leg_labels())
-    return (_mpo_entries(W0) is not None and _mpo_entries(W1) is not None and
-            sorted(lp) == sorted(['vR*', 'wR', 'vR']) and lp.index('vR*') < lp.index('vR') and
-            sorted(rp) == sorted(['wL', 'vL', 'vL*']) and rp.index('vL') < rp.index('vL*') and
-            bool(np.all(LP.get_leg('wR').get_block_sizes() == 1)) and bool(np.all(RP.get_leg('wL').get_block_sizes() == 1)) and
+    return (_mpo_entries(W0) is not None and _mpo_entries(W1) is not None and _envs_factorable(LP, RP) and
             w0 in (['wL', 'wR', 'p0', 'p0*'], ['wL', 'wR', 'p', 'p*']) and w1 in (['wL', 'wR', 'p1', 'p1*'], ['wL', 'wR', 'p', 'p*']))
 
 
@@ -390,7 +395,49 @@ def _gemm_ops(plan, a_slot, b_slot, c_slot, bufs, scratch_name):
             [1, 1, sk.jobs_dev.data_ptr(), sk.terms_dev.data_ptr(), 0, sk.n_jobs, part, 0, c_slot, sk.max_elems, 0, 0]]
 
 
-class TwoSiteH:
+class _DeviceEffectiveH:
+    """What the device forms of the effective Hamiltonians share: the hand-over of a vector to ``tpa_lanczos_run``.  A subclass
+    provides ``matvec_program(theta)`` (see :meth:`TwoSiteH.matvec_program`), which ends in :meth:`_file_program`."""
+
+    def _file_program(self, theta, res, last):
+        """Keep the program ``res`` of a contraction chain ending in plan ``last`` for ``theta``'s structure -- or, when the chain's
+        output has another block structure than its input (no replay on raw arenas), that structure for :meth:`native_input`."""
+        key = (theta._struct_key(), theta.dtype)
+        self.__dict__['_program_out'] = None
+        if res is not None and not (last.res_total == theta._arena.numel() and np.array_equal(last.res_qdata, theta._qdata)
+                                    and np.array_equal(last.res_offsets, theta._offsets)):
+            self.__dict__['_program_out'] = (key, last.res_qdata, last.res_offsets, last.res_total)
+            res = None
+        self.__dict__['_program'] = (key, res)
+        return res
+
+    def native_input(self, theta, max_pad=2):
+        """``(vector, program)`` for ``tpa_lanczos_run``: ``theta`` itself, or -- when H_eff creates blocks that ``theta`` does not
+        store (tiny extreme charge sectors of a state grown from a product state: the first Krylov step of the step-by-step
+        loop goes the generic way for them) -- ``theta`` embedded with zero blocks in the block structure of ``H_eff theta``,
+        provided that structure is closed under another application.  ``None`` if no replayable program exists."""
+        vec = theta
+        for _ in range(max_pad + 1):
+            prog = self.matvec_program(vec)
+            if prog is not None:
+                return vec, prog
+            out = self.__dict__.get('_program_out')
+            if out is None or out[0] != (vec._struct_key(), vec.dtype):
+                return None
+            _, qdata, offsets, total = out
+            have = {tuple(r) for r in qdata.tolist()}
+            if not all(tuple(r) in have for r in vec._qdata.tolist()):
+                return None                      # H_eff theta lacks blocks of theta: not an embedding
+            pad = npc.Array(vec.legs, vec.dtype, vec.qtotal, vec.get_leg_labels())
+            pad._set_blocks(qdata, arena=dev.zeros(total, vec.dtype), qdata_sorted=True)
+            if not np.array_equal(pad._offsets, offsets):
+                return None
+            npc._scatter_blocks(vec, pad, pad._arena)
+            vec = pad
+        return None
+
+
+class TwoSiteH(_DeviceEffectiveH):
     length = 2
     acts_on = ['(vL.p0)', '(p1.vR)']
 
@@ -524,6 +571,8 @@ class TwoSiteH:
         T1 = LP . theta (GEMM, contracted index = chi, not d chi);  T3 = MPO tensors applied blockwise (lincomb);
         theta' = T3 . RP (GEMM, chain over wR and the bond sector)."""
         fp = self._fplans
+        if fp is not None and (fp['lkey'] != self._LPf._struct_key() or fp['rkey'] != self._RPf._struct_key()):
+            fp = None               # plans handed over from an earlier visit of the bond: the environments changed shape since
         if fp is None or fp['key'] != theta._struct_key() or fp['dtype'] != theta.dtype:
             p1, l_use, t_use = npc.plan_tensordot(self._LPf, theta, axes=['vR', 'vL'])
             assert l_use is self._LPf and t_use is theta, "factored matvec step 1 must not need a transpose"
@@ -533,7 +582,8 @@ class TwoSiteH:
             T3 = a01.apply(T1)
             p2, t3_use, r_use = npc.plan_tensordot(T3, self._RPf, axes=(['wR', 'vR'], ['wL', 'vL']))
             assert t3_use is T3 and r_use is self._RPf, "factored matvec step 2 must not need a transpose"
-            self._fplans = dict(key=theta._struct_key(), dtype=theta.dtype, p1=p1, a01=a01, p2=p2)
+            self._fplans = dict(key=theta._struct_key(), dtype=theta.dtype, p1=p1, a01=a01, p2=p2,
+                                lkey=self._LPf._struct_key(), rkey=self._RPf._struct_key())
             if not p1.empty and not p2.empty:
                 self.flops_per_matvec = p1.flops + p2.flops
                 self.bytes_per_matvec = p1.bytes_min + p2.bytes_min + a01.bytes
@@ -588,7 +638,7 @@ class TwoSiteH:
         res = None
         if self.factored:
             fp = self._fplans
-            if fp is not None and 'lkey' in fp and (fp['lkey'] != self._LPf._struct_key() or fp['rkey'] != self._RPf._struct_key()):
+            if fp is not None and (fp['lkey'] != self._LPf._struct_key() or fp['rkey'] != self._RPf._struct_key()):
                 fp = None           # (plans handed over from the previous visit of this bond, `plan_cache`: the environments changed shape)
             if fp is None or fp['key'] != theta._struct_key() or fp['dtype'] != theta.dtype:
                 p1, l_use, t_use = npc.plan_tensordot(self._LPf, theta, axes=['vR', 'vL'])
@@ -638,38 +688,7 @@ class TwoSiteH:
                 ops = _gemm_ops(p1, 0, -1, 2, bufs, 'lanczos_sk1') + _gemm_ops(p2, 2, 1, -2, bufs, 'lanczos_sk2')
                 res = (np.array(ops, dtype=np.int64), bufs, (p1, p2))
                 last = p2
-        self.__dict__['_program_out'] = None
-        if res is not None and not (last.res_total == theta._arena.numel() and np.array_equal(last.res_qdata, theta._qdata)
-                                    and np.array_equal(last.res_offsets, theta._offsets)):
-            self.__dict__['_program_out'] = (key, last.res_qdata, last.res_offsets, last.res_total)
-            res = None
-        self.__dict__['_program'] = (key, res)
-        return res
-
-    def native_input(self, theta, max_pad=2):
-        """``(vector, program)`` for ``tpa_lanczos_run``: ``theta`` itself, or -- when H_eff creates blocks that ``theta`` does not
-        store (tiny extreme charge sectors of a state grown from a product state: the first Krylov step of the step-by-step
-        loop goes the generic way for them) -- ``theta`` embedded with zero blocks in the block structure of ``H_eff theta``,
-        provided that structure is closed under another application.  ``None`` if no replayable program exists."""
-        vec = theta
-        for _ in range(max_pad + 1):
-            prog = self.matvec_program(vec)
-            if prog is not None:
-                return vec, prog
-            out = self.__dict__.get('_program_out')
-            if out is None or out[0] != (vec._struct_key(), vec.dtype):
-                return None
-            _, qdata, offsets, total = out
-            have = {tuple(r) for r in qdata.tolist()}
-            if not all(tuple(r) in have for r in vec._qdata.tolist()):
-                return None                      # H_eff theta lacks blocks of theta: not an embedding
-            pad = npc.Array(vec.legs, vec.dtype, vec.qtotal, vec.get_leg_labels())
-            pad._set_blocks(qdata, arena=dev.zeros(total, vec.dtype), qdata_sorted=True)
-            if not np.array_equal(pad._offsets, offsets):
-                return None
-            npc._scatter_blocks(vec, pad, pad._arena)
-            vec = pad
-        return None
+        return self._file_program(theta, res, last if res is not None else None)
 
     def _plan_matches(self, theta):
         return self._plans[2] == theta._struct_key() and self._plans[3] == theta.dtype
@@ -719,3 +738,160 @@ class TwoSiteH:
         full = full.transpose(0, 3, 1, 2)                    # out_L, out_R, in_L, in_R
         n = full.shape[0] * full.shape[1]
         return full.reshape(n, n)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# One- and zero-site effective Hamiltonians (TDVP: ``one_site_update`` after every two-site update, ``zero_site_update`` after
+# every one-site update of the single-site algorithm), in the factored form of ``TwoSiteH``:
+#     one site   theta [vL, p0, vR]:  T1 = LP . theta (grouped GEMM),  T2 = W0 applied blockwise (MpoApplyPlan),
+#                                     theta' = T2 . RP (grouped GEMM chained over wR and the bond sector)
+#     zero sites theta [vL, vR]    :  T1 = LP . theta,  theta' = T1 . RP chained over (wR, vR)
+# instead of three generic tensordots with transposed copies and a K = 1 GEMM per MPO entry (reference mps_common.py:1146-1149,
+# :1512-1514).
+class _LocalH(_DeviceEffectiveH):
+    combine = False
+    move_right = True
+
+    def _setup(self, LP, W0, RP, i0, dtype):
+        self.i0 = i0
+        self.LP, self.RP = LP, RP
+        self.W0 = None
+        if W0 is not None:
+            self.W0 = W0.replace_labels(['p', 'p*'], ['p0', 'p0*'])
+            self.W0._tpa_entries = _mpo_entries(W0)      # (host copy of the entries: cached on the MPO's own tensor)
+        self.dtype = dtype
+        self._fplans = None
+        self.factored = _envs_factorable(LP, RP) and (W0 is None or (
+            _mpo_entries(W0) is not None and list(self.W0.get_leg_labels()) == ['wL', 'wR', 'p0', 'p0*']))
+        if self.factored:
+            self._LPf = _relabel_view(LP, ['vR*', 'wR', 'vR'])
+            self._RPf = _relabel_view(RP, ['wL', 'vL', 'vL*'])
+        n = LP.get_leg('vR').ind_len * RP.get_leg('vL').ind_len
+        self.N = n if W0 is None else n * self.W0.get_leg('p0').ind_len
+
+    def _plans(self, theta):
+        """The cached plans of the three (two) steps for this ``theta`` -- rebuilt whenever the block structure of ``theta`` OR of an
+        environment differs from the one they were made for (plans are handed from visit to visit of a site while the
+        environments grow); ``None`` when a step would need a transposed copy or contributes nothing."""
+        fp = self._fplans
+        tkey, lkey, rkey = theta._struct_key(), self._LPf._struct_key(), self._RPf._struct_key()
+        if fp is not None and fp['key'] == tkey and fp['dtype'] == theta.dtype and fp['lkey'] == lkey and fp['rkey'] == rkey:
+            return fp
+        self._fplans = None
+        p1, l_use, t_use = npc.plan_tensordot(self._LPf, theta, axes=['vR', 'vL'])
+        if l_use is not self._LPf or t_use is not theta or p1.empty:
+            return None
+        T = p1.apply(self._LPf, theta, launch=False)               # vR*, wR, [p0,] vR
+        a0 = None
+        if self.W0 is not None:
+            a0 = MpoApplyPlan.get(T, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'wR', 'vR'))
+            if a0.empty:
+                return None
+            T = a0.apply(T, launch=False)                          # vR*, p0, wR, vR
+        p2, t_use, r_use = npc.plan_tensordot(T, self._RPf, axes=(['wR', 'vR'], ['wL', 'vL']))
+        if t_use is not T or r_use is not self._RPf or p2.empty:
+            return None
+        self._fplans = fp = dict(key=tkey, dtype=theta.dtype, lkey=lkey, rkey=rkey, p1=p1, a0=a0, p2=p2)
+        return fp
+
+    def matvec(self, theta):
+        """``theta`` with the labels of ``acts_on`` (any order) -> ``H_eff theta``, same legs and labels."""
+        labels = list(theta.get_leg_labels())
+        if labels != self.acts_on:
+            theta = theta.transpose(self.acts_on)
+        fp = self._plans(theta) if (self.factored and theta.stored_blocks > 0) else None
+        if fp is not None:
+            T = fp['p1'].apply(self._LPf, theta)
+            if fp['a0'] is not None:
+                T = fp['a0'].apply(T)
+            res = fp['p2'].apply(T, self._RPf)
+        else:               # the reference's contractions (MPO blocks that are not single numbers, no charges, empty theta)
+            res = npc.tensordot(self.LP, theta, axes=['vR', 'vL'])
+            if self.W0 is not None:
+                res = npc.tensordot(self.W0, res, axes=[['wL', 'p0*'], ['wR', 'p0']])
+            res = npc.tensordot(res, self.RP, axes=[['wR', 'vR'], ['wL', 'vL']])
+            res = res.replace_labels(['vR*', 'vL*'], ['vL', 'vR']).transpose(self.acts_on)
+        res.iset_leg_labels(self.acts_on)
+        return res if labels == self.acts_on else res.transpose(labels)
+
+    def matvec_program(self, theta):
+        """The matvec as a launch program for ``tpa_lanczos_run`` (format: :meth:`TwoSiteH.matvec_program`), or ``None``: no factored
+        form, vector not in the order of ``acts_on``, mixed dtypes, or an output block structure other than the input's."""
+        if not self.factored or list(theta.get_leg_labels()) != self.acts_on or theta.stored_blocks == 0 or not theta._is_packed():
+            return None
+        key = (theta._struct_key(), theta.dtype)
+        prog = self.__dict__.get('_program')
+        if prog is not None and prog[0] == key:
+            return prog[1]
+        fp = self._plans(theta)
+        res = last = None
+        if fp is not None:
+            p1, a0, p2 = fp['p1'], fp['a0'], fp['p2']
+            if p1.dtype == p2.dtype == theta.dtype == self._LPf.dtype == self._RPf.dtype and (a0 is None or a0.dtype == theta.dtype):
+                bufs = [self._LPf._arena, self._RPf._arena, dev.scratch('lanczos_t1', p1.res_total, p1.dtype)]
+                ops = _gemm_ops(p1, 0, -1, 2, bufs, 'lanczos_sk1')
+                src = 2
+                if a0 is not None:
+                    bufs.append(dev.scratch('lanczos_t3', a0.total, a0.dtype))
+                    src = len(bufs) - 1
+                    ops.append([1, 0, a0.jobs_dev.data_ptr(), a0.terms_dev.data_ptr(), 0, a0.n_jobs, 2, 0, src, a0.max_elems, 0, 0])
+                ops += _gemm_ops(p2, src, 1, -2, bufs, 'lanczos_sk2')
+                res, last = (np.array(ops, dtype=np.int64), bufs, (p1, p2)), p2
+        return self._file_program(theta, res, last)
+
+    def to_matrix(self):
+        """``self`` contracted to a matrix ``[(vR*.p0.vL*), (vR.p0*.vL)]`` (reference :1205-1207, :1520-1521)."""
+        contr = self.LP
+        if self.W0 is not None:
+            contr = npc.tensordot(contr, self.W0, axes=['wR', 'wL'])
+        contr = npc.tensordot(contr, self.RP, axes=['wR', 'wL'])
+        if self.W0 is not None:
+            return contr.combine_legs([['vR*', 'p0', 'vL*'], ['vR', 'p0*', 'vL']], qconj=[+1, -1])
+        return contr.combine_legs([['vR*', 'vL*'], ['vR', 'vL']], qconj=[+1, -1])
+
+
+class OneSiteH(_LocalH):
+    """Effective one-site Hamiltonian ``LP - W0 - RP`` acting on ``theta [vL, p0, vR]`` (reference ``OneSiteH``,
+    mps_common.py:1040) for ``combine=False``, which is what TDVP uses."""
+    length = 1
+    acts_on = ['vL', 'p0', 'vR']
+
+    def __init__(self, env, i0, combine=False, move_right=True):
+        if combine:
+            raise NotImplementedError("tenpy_amd.OneSiteH (stand-alone driver): only combine=False")
+        self.move_right = move_right
+        self._setup(env.get_LP(i0), env.H.get_W(i0), env.get_RP(i0), i0, env.H.dtype)
+
+    @classmethod
+    def from_LP_W0_RP(cls, LP, W0, RP, i0=0, combine=False, move_right=True):
+        if combine:
+            raise NotImplementedError("tenpy_amd.OneSiteH: only combine=False")
+        self = cls.__new__(cls)
+        self.move_right = move_right
+        self._setup(LP.transpose(['vR*', 'wR', 'vR']), W0, RP.transpose(['wL', 'vL', 'vL*']), i0, LP.dtype)
+        return self
+
+    def combine_theta(self, theta):
+        return theta if list(theta.get_leg_labels()) == self.acts_on else theta.transpose(self.acts_on)
+
+    def update_LP(self, env, i, U=None):
+        env.get_LP(i, store=True)
+
+    def update_RP(self, env, i, VH=None):
+        env.get_RP(i, store=True)
+
+
+class ZeroSiteH(_LocalH):
+    """Effective zero-site Hamiltonian ``LP - RP`` acting on the bond matrix ``theta [vL, vR]`` left of site ``i0`` (reference
+    ``ZeroSiteH``, mps_common.py:1440)."""
+    length = 0
+    acts_on = ['vL', 'vR']
+
+    def __init__(self, env, i0):
+        self._setup(env.get_LP(i0), None, env.get_RP(i0 - 1), i0, env.H.dtype)
+
+    @classmethod
+    def from_LP_RP(cls, LP, RP, i0=0):
+        self = cls.__new__(cls)
+        self._setup(LP.transpose(['vR*', 'wR', 'vR']), None, RP.transpose(['wL', 'vL', 'vL*']), i0, LP.dtype)
+        return self

@@ -353,6 +353,76 @@ __global__ __launch_bounds__(NT) void krylov_combine_kernel(int64_t nd, int N, L
     }
 }
 
+// ---- the same combination with COMPLEX coefficients: exp(delta h) e_0 of LanczosEvolution --------------------------------------
+// Replaces, for `LanczosEvolution.run` (reference krylov_based.py:757-795), the N flat axpy passes (or, real Krylov vectors
+// with an imaginary delta, the N generic iadd_prefactor_other calls) of `_calc_result_full` (reference :160-198):
+//     out = scale * sum_{k<N} c_k V_k ,  partial |sum_k c_k V_k|^2 per workgroup (BEFORE the scale).
+// One pass over the N + 1 vectors, HBM bound (itemsize n (N + 1) bytes).  The basis is real or complex (template, no branch per
+// element), `out` is always complex.  VEC: 16-byte loads -- one complex or two real elements of every V_k per thread and step,
+// 16-byte stores; the coefficients are kernel arguments (k is uniform: scalar loads from the argument segment).  The scalar
+// form (8-byte loads) serves a real basis with odd n -- every second V_k then starts 8 bytes off a 16-byte boundary, there is no
+// aligned body to peel a tail from -- and base addresses that are not 16-byte aligned.
+// `scale` is applied here because its value (|psi0| |exp(delta h) e_0|, or 1) is known before the pass and costs no traffic; the
+// division by the returned norm is the caller's (`tpa_scal`): it has to look at that norm on the host anyway (ill-conditioned
+// warning, degenerate fallback to the start vector), so a second device pass fed from device memory would save no wait.
+struct LzCoeffZ {
+    double2 c[LZ_MAX_COMBINE];
+};
+
+template <bool CPLX, bool VEC>
+__global__ __launch_bounds__(NT) void krylov_combine_z_kernel(int64_t n_items, int N, LzCoeffZ C, double scale, const double *__restrict__ V,
+                                                              int64_t stride, double *__restrict__ out, double *__restrict__ partial) {
+    __shared__ double red[NT / 64];
+    constexpr int W = (CPLX || VEC) ? 2 : 1;       // doubles of one V_k per item
+    double s = 0;
+    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n_items; i += (int64_t)gridDim.x * NT) {
+        const double *p = V + W * i;
+        double re0 = 0, im0 = 0, re1 = 0, im1 = 0;
+#pragma unroll 4
+        for (int k = 0; k < N; ++k) {
+            const double2 c = C.c[k];
+            double2 v;
+            if (VEC) {
+                v = *reinterpret_cast<const double2 *>(p + k * stride);
+            } else {
+                v.x = p[k * stride];
+                v.y = CPLX ? p[k * stride + 1] : 0.;
+            }
+            if (CPLX) {
+                re0 = fma(c.x, v.x, re0);
+                re0 = fma(-c.y, v.y, re0);
+                im0 = fma(c.x, v.y, im0);
+                im0 = fma(c.y, v.x, im0);
+            } else {
+                re0 = fma(c.x, v.x, re0);
+                im0 = fma(c.y, v.x, im0);
+                if (VEC) {
+                    re1 = fma(c.x, v.y, re1);
+                    im1 = fma(c.y, v.y, im1);
+                }
+            }
+        }
+        s = fma(re0, re0, s);
+        s = fma(im0, im0, s);
+        if (!CPLX && VEC) {
+            s = fma(re1, re1, s);
+            s = fma(im1, im1, s);
+            reinterpret_cast<double2 *>(out)[2 * i] = double2{scale * re0, scale * im0};
+            reinterpret_cast<double2 *>(out)[2 * i + 1] = double2{scale * re1, scale * im1};
+        } else if (VEC) {
+            reinterpret_cast<double2 *>(out)[i] = double2{scale * re0, scale * im0};
+        } else {
+            out[2 * i] = scale * re0;
+            out[2 * i + 1] = scale * im0;
+        }
+    }
+    s = block_sum<NT>(s, red);
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x] = s;
+        partial[2 * blockIdx.x + 1] = 0.;
+    }
+}
+
 __global__ void lz_post_scalars_kernel(const double *__restrict__ src, double *__restrict__ dst_host) {
     dst_host[0] = src[0];
     dst_host[1] = src[1];
@@ -532,6 +602,44 @@ extern "C" int tpa_krylov_combine(int dtype, int64_t n, const void *krylov_dev, 
         krylov_combine_kernel<true><<<g, NT, 0, st>>>(nd, N, C, (const double *)krylov_dev, nd, (double *)out_dev, scratch_dev);
     else
         krylov_combine_kernel<false><<<g, NT, 0, st>>>(nd, N, C, (const double *)krylov_dev, nd, (double *)out_dev, scratch_dev);
+    reduce_pass2<<<1, NT, 0, st>>>(g, scratch_dev, red_out_dev);
+    TPA_LAUNCH_CHECK();
+    if (int rc = lz_reserve(1)) return rc;
+    lz_post_scalars_kernel<<<1, 1, 0, st>>>(red_out_dev, lz_host.pinned);
+    TPA_HIP_CHECK(hipEventRecord(lz_host.ev[0], st));
+    TPA_HIP_CHECK(hipEventSynchronize(lz_host.ev[0]));
+    norm_host[0] = sqrt(lz_host.pinned[0]);
+    return 0;
+}
+
+// out = scale * sum_{k < N} c_k v_k with complex c_k (host: N pairs re, im), basis F64 or C128, out C128; norm_host[0] = |sum_k c_k v_k|
+// (before `scale`, blocking).  See krylov_combine_z_kernel for what it replaces and why the normalisation stays with the caller.
+extern "C" int tpa_krylov_combine_z(int basis_dtype, int64_t n, const void *krylov_dev, int N, const double *coeff, double scale,
+                                    void *out_dev, double *red_out_dev, double *scratch_dev, double *norm_host, void *stream) {
+    TPA_ARG_CHECK(basis_dtype == TPA_F64 || basis_dtype == TPA_C128);
+    TPA_ARG_CHECK(n > 0 && N >= 1 && N <= LZ_MAX_COMBINE && krylov_dev != nullptr && coeff != nullptr && out_dev != nullptr);
+    TPA_ARG_CHECK(red_out_dev != nullptr && scratch_dev != nullptr && norm_host != nullptr);
+    hipStream_t st = (hipStream_t)stream;
+    const bool cplx = (basis_dtype == TPA_C128);
+    LzCoeffZ C;
+    for (int k = 0; k < LZ_MAX_COMBINE; ++k) C.c[k] = k < N ? double2{coeff[2 * k], coeff[2 * k + 1]} : double2{0., 0.};
+    const bool aligned = (((uintptr_t)krylov_dev | (uintptr_t)out_dev) & 15) == 0;
+    const bool vec = aligned && (cplx || n % 2 == 0);
+    const int64_t n_items = (!cplx && vec) ? n / 2 : n;
+    const int64_t stride = cplx ? 2 * n : n;            // doubles from V_k to V_{k+1}
+    int64_t g64 = (n_items + NT - 1) / NT;
+    const int g = (int)(g64 > 2 * MAXBLK ? 2 * MAXBLK : g64);       // 2 doubles per workgroup in scratch_dev (TPA_RED_SCRATCH = 4 MAXBLK)
+    const double *V = (const double *)krylov_dev;
+    double *out = (double *)out_dev;
+    if (cplx && vec)
+        krylov_combine_z_kernel<true, true><<<g, NT, 0, st>>>(n_items, N, C, scale, V, stride, out, scratch_dev);
+    else if (cplx)
+        krylov_combine_z_kernel<true, false><<<g, NT, 0, st>>>(n_items, N, C, scale, V, stride, out, scratch_dev);
+    else if (vec)
+        krylov_combine_z_kernel<false, true><<<g, NT, 0, st>>>(n_items, N, C, scale, V, stride, out, scratch_dev);
+    else
+        krylov_combine_z_kernel<false, false><<<g, NT, 0, st>>>(n_items, N, C, scale, V, stride, out, scratch_dev);
+    TPA_LAUNCH_CHECK();
     reduce_pass2<<<1, NT, 0, st>>>(g, scratch_dev, red_out_dev);
     TPA_LAUNCH_CHECK();
     if (int rc = lz_reserve(1)) return rc;

@@ -17,8 +17,9 @@ a TeNPy that keeps its own ``np_conserved`` -- is ``tenpy_amd/_npc_helper.py``.
 
 ``install(fused=True)`` additionally rebinds, after ``import tenpy``, the callers for which the device has a
 fused form: ``LanczosGroundState`` (one fused recurrence kernel per step instead of four BLAS-1 calls), ``TwoSiteH``
-(cached plans; factored matvec LP . theta . W0 W1 . RP for ``combine=False``) and the bond hint of the warm-started block
-SVD; see :func:`use_fused_callers`.
+(cached plans; factored matvec LP . theta . W0 W1 . RP for ``combine=False``), the bond hint of the warm-started block
+SVD, and for TDVP ``LanczosEvolution`` (one native loop and one combination pass per evolution) with the device ``OneSiteH`` /
+``ZeroSiteH``; see :func:`use_fused_callers`.
 """
 import importlib
 import importlib.abc
@@ -103,6 +104,13 @@ def use_fused_callers():
     * ``TwoSiteDMRGEngine.mixed_svd`` (``dmrg.py:876``) is wrapped to pass the bond index to the block SVD (warm start).
     * ``TEBDEngine.evolve_step`` (``tebd.py:374``; inherited by ``QRBasedTEBDEngine``) -> the bonds of a half-step decomposed in one
       batched device call (``module_form.batched_tebd_evolve_step``; the per-bond statements stay the reference's).
+    * ``LanczosEvolution`` (``linalg/krylov_based.py:718``; constructed at ``tdvp.py:132 _krylov_evolve``) -> the device class: the
+      whole Krylov loop as one ``tpa_lanczos_run`` call and the result as one pass over the Krylov vectors with complex coefficients (plus the normalising ``tpa_scal``), where the operator
+      offers a launch program; ``OneSiteH`` / ``ZeroSiteH`` (``mps_common.py:1040`` / ``:1440``; ``tdvp.py:308`` / ``:419``) -> the
+      device forms of ``module_form`` (factored matvec with cached plans), which hand what they do not cover back to the
+      reference's classes; ``TwoSiteTDVPEngine.EffectiveH`` / ``SingleSiteTDVPEngine.EffectiveH`` (``tdvp.py:248`` / ``:333``) get the
+      device ``TwoSiteH`` / ``OneSiteH``, so that the forward evolutions run natively too.  ``OneSiteH`` / ``ZeroSiteH`` are rebound in
+      ``mps_common`` and ``tdvp`` only: DMRG, VUMPS and the plane-wave excitations keep theirs.
     """
     import tenpy.algorithms.dmrg as ref_dmrg
     import tenpy.algorithms.mps_common as ref_mc
@@ -121,3 +129,13 @@ def use_fused_callers():
     import tenpy.algorithms.tebd as ref_tebd
     if not getattr(ref_tebd.TEBDEngine.evolve_step, '_tpa_wrapped', False):
         ref_tebd.TEBDEngine.evolve_step = module_form.batched_tebd_evolve_step(ref_tebd)
+    import tenpy.algorithms.tdvp as ref_tdvp
+    ref_kb.LanczosEvolution = kb.LanczosEvolution
+    ref_tdvp.LanczosEvolution = kb.LanczosEvolution
+    if not hasattr(ref_mc.OneSiteH, '_reference_class'):
+        ref_mc.OneSiteH = ref_tdvp.OneSiteH = module_form.device_one_site_h(ref_mc.OneSiteH)
+    # `import tenpy` has imported tdvp already: the names and class attributes bound there are re-pointed one by one
+    ref_tdvp.TwoSiteH = ref_tdvp.TwoSiteTDVPEngine.EffectiveH = ref_mc.TwoSiteH
+    ref_tdvp.SingleSiteTDVPEngine.EffectiveH = ref_mc.OneSiteH
+    if not hasattr(ref_mc.ZeroSiteH, '_reference_class'):
+        ref_mc.ZeroSiteH = ref_tdvp.ZeroSiteH = module_form.device_zero_site_h(ref_mc.ZeroSiteH)

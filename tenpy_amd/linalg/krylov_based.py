@@ -1,4 +1,4 @@
-"""Lanczos ground-state search on device-resident block vectors.
+"""Lanczos ground-state search and Krylov time evolution on device-resident block vectors.
 
 Mirrors ``tenpy/linalg/krylov_based.py`` (``KrylovBased`` :28, ``LanczosGroundState`` :584,
 ``_build_krylov`` :645, ``_converged`` :678, ``_calc_result_full`` :160) -- same options, same
@@ -9,6 +9,11 @@ convergence criteria, same returned triple ``(E0, psi0, N)`` -- but the three-te
 * ``w -= alpha v_k ; w -= beta v_{k-1} ; |w|^2`` is a single kernel (``tpa_lanczos_update``) instead of
   two axpy + a norm (reference :665-672); alpha and beta are the only two host synchronisations per
   iteration (the tridiagonal ``eigh`` stays on the host).
+
+Where the operator hands over its matvec as a launch program (``native_input``: the device forms of ``TwoSiteH``, ``OneSiteH``,
+``ZeroSiteH``) the whole Krylov loop is one C-ABI call (``tpa_lanczos_run``), shared by ``LanczosGroundState`` and
+``LanczosEvolution`` (:meth:`LanczosGroundState._native_krylov`); the two differ in the result step: ``tpa_krylov_combine`` with the
+real ground state of the tridiagonal matrix, ``tpa_krylov_combine_z`` with the complex ``exp(delta h) e_0``.
 """
 import logging
 
@@ -26,7 +31,7 @@ PIPELINED = _os.environ.get('TPA_LANCZOS_PIPELINED', '1') != '0'     # device-re
 __all__ = ['LanczosGroundState', 'LanczosEvolution', 'Arnoldi', 'lanczos', 'gram_schmidt', 'iscale_prefactor', 'iadd_prefactor_other']
 
 
-stats = {'runs': 0, 'n_matvec': 0, 'n_ill_conditioned': 0, 'n_degenerate': 0, 'n_native_sharded': 0}
+stats = {'runs': 0, 'n_matvec': 0, 'n_ill_conditioned': 0, 'n_degenerate': 0, 'n_native_sharded': 0, 'n_native_evolve': 0}
 
 
 class LanczosGroundState:
@@ -93,9 +98,45 @@ class LanczosGroundState:
         return prog
 
     def _run_native(self, prog):
-        """``_build_krylov`` + ``_calc_result_full`` through ``tpa_lanczos_run`` / ``tpa_krylov_combine``: the device side of every
-        step is enqueued by a C++ loop, the reference's host side of a step (tridiagonal ``eigh``, ``_converged``) runs in the
-        callback one step late -- the same numbers as :meth:`_build_krylov_pipelined`, without ~0.5 ms of interpreter time per step.
+        """``_build_krylov`` + ``_calc_result_full`` through ``tpa_lanczos_run`` / ``tpa_krylov_combine``: the loop of
+        :meth:`_native_krylov`, then the ground state of the tridiagonal matrix combined in one pass."""
+        N, n, krylov, red = self._native_krylov(prog)
+        L, w = dev.lib(), self.psi0
+        code = dev.code(w.dtype)
+        _, scr = dev.reduction_buffers()
+        E0 = self.Es[N - 1, 0]
+        if self.E_shift is not None:
+            E0 -= self.E_shift
+        psif = w.copy(deep=False)
+        out = dev.empty(n, w.dtype)
+        if N == 1:
+            out.copy_(krylov[:n])
+            psif._arena = out
+            return E0, psif, N
+        vf = np.ascontiguousarray(self._result_krylov, dtype=np.float64)
+        assert len(vf) == N
+        nrm = np.zeros(1, dtype=np.float64)
+        dev.check(L.tpa_krylov_combine(code, n, krylov.data_ptr(), N, vf.ctypes.data, out.data_ptr(), red, scr.data_ptr(), nrm.ctypes.data,
+                                       dev.stream()), "krylov_combine")
+        nrm = float(nrm[0])
+        psif._arena = out
+        if abs(1. - nrm) > 1.e-5:
+            stats['n_ill_conditioned'] += 1
+            logger.warning("poorly conditioned H matrix in KrylovBased! |psi_0| = %f", nrm)
+        if not (nrm > 1.e-8) or not np.isfinite(nrm):      # see _calc_result_full
+            stats['n_degenerate'] += 1
+            out.copy_(krylov[:n])
+            nrm = 1.
+        if nrm != 1.:
+            dev.check(L.tpa_scal(code, n, 1. / nrm, 0., out.data_ptr(), dev.stream()), "scal")
+        return E0, psif, N
+
+    def _native_krylov(self, prog):
+        """``_build_krylov`` through ``tpa_lanczos_run``: the device side of every step is enqueued by a C++ loop, the reference's host
+        side of a step (tridiagonal ``eigh`` in ``_calc_result_krylov``, ``_converged`` -- the two methods a subclass overrides) runs in
+        the callback one step late -- the same numbers as :meth:`_build_krylov_pipelined`, without ~0.5 ms of interpreter time per
+        step.  Returns ``(N, n, krylov, red)``: the Krylov ONB ``v_k = krylov[k n:(k + 1) n]`` on the device and the address of two
+        device doubles for the reduction of the result step.
 
         Sharded operators (``collective`` callback): the failure agreement at the end only covers errors raised AFTER the run's last
         collective.  A rank that fails mid-run (HIP error, or the collective callback returning 1) reaches the agreement all-reduce while
@@ -180,32 +221,7 @@ class LanczosGroundState:
             raise ValueError("Norm of self.psi0 too small: {0}".format(info[3]))
         if self._psi0_norm is None:
             self._psi0_norm = float(info[3])
-        E0 = self.Es[N - 1, 0]
-        if self.E_shift is not None:
-            E0 -= self.E_shift
-        psif = w.copy(deep=False)
-        out = dev.empty(n, dtype)
-        if N == 1:
-            out.copy_(krylov[:n])
-            psif._arena = out
-            return E0, psif, N
-        vf = np.ascontiguousarray(self._result_krylov, dtype=np.float64)
-        assert len(vf) == N
-        nrm = np.zeros(1, dtype=np.float64)
-        dev.check(L.tpa_krylov_combine(code, n, krylov.data_ptr(), N, vf.ctypes.data, out.data_ptr(), scal.data_ptr() + 8 * 2 * (N_max + 2),
-                                       scr.data_ptr(), nrm.ctypes.data, dev.stream()), "krylov_combine")
-        nrm = float(nrm[0])
-        psif._arena = out
-        if abs(1. - nrm) > 1.e-5:
-            stats['n_ill_conditioned'] += 1
-            logger.warning("poorly conditioned H matrix in KrylovBased! |psi_0| = %f", nrm)
-        if not (nrm > 1.e-8) or not np.isfinite(nrm):      # see _calc_result_full
-            stats['n_degenerate'] += 1
-            out.copy_(krylov[:n])
-            nrm = 1.
-        if nrm != 1.:
-            dev.check(L.tpa_scal(code, n, 1. / nrm, 0., out.data_ptr(), dev.stream()), "scal")
-        return E0, psif, N
+        return N, n, krylov, scal.data_ptr() + 8 * 2 * (N_max + 2)
 
     # ---- internals ------------------------------------------------------------------------------------------
     def _matvec(self, w):
@@ -422,16 +438,76 @@ class LanczosEvolution(LanczosGroundState):
     def run(self, delta, normalize=None):
         """Returns ``(psi_f, N)``; ``normalize`` defaults to ``real(delta) == 0`` (unitary evolution)."""
         self.delta = delta
+        if normalize is None:
+            normalize = np.real(delta) == 0.
+        prog = self._native_program()
+        if prog is not None:
+            return self._run_native(prog, normalize)
         N = self._build_krylov()
         if N == 1:
             result_full = self.psi0 * self._result_krylov[0]      # only a phase
         else:
             result_full = self._calc_result_full(N)
-        if normalize is None:
-            normalize = np.real(delta) == 0.
         if normalize:
             return result_full, N
         return result_full * (self._psi0_norm * self._result_norm), N
+
+    def _run_native(self, prog, normalize):
+        """The Krylov loop of the ground-state search (:meth:`_native_krylov`; the callback dispatches to the ``_calc_result_krylov`` /
+        ``_converged`` of this class), then ``psi = scale sum_k c_k v_k`` with ``c = exp(delta h) e_0 / |..|`` in one pass over the Krylov vectors (the
+        division by the returned norm is a ``tpa_scal`` on the result afterwards):
+        ``tpa_krylov_combine_z`` (complex result, also from real Krylov vectors) or -- real ``c``, imaginary time: the reference
+        keeps the dtype of the vectors -- ``tpa_krylov_combine``.  ``scale = |psi0| |exp(delta h) e_0|`` unless ``normalize``."""
+        stats['n_native_evolve'] += 1
+        N, n, krylov, red = self._native_krylov(prog)
+        L, w, st = dev.lib(), self.psi0, dev.stream()
+        code = dev.code(w.dtype)
+        _, scr = dev.reduction_buffers()
+        scale = 1. if normalize else float(self._psi0_norm * self._result_norm)
+        c = np.asarray(self._result_krylov)
+        assert len(c) == N
+        psif = w.copy(deep=False)
+        nrm = np.zeros(1, dtype=np.float64)
+        if c.dtype.kind != 'c':
+            out = dev.empty(n, w.dtype)
+            psif._arena = out
+            vf = np.ascontiguousarray(c, dtype=np.float64)
+            dev.check(L.tpa_krylov_combine(code, n, krylov.data_ptr(), N, vf.ctypes.data, out.data_ptr(), red, scr.data_ptr(),
+                                           nrm.ctypes.data, st), "krylov_combine")
+            if N > 1 and self._check_result_norm(float(nrm[0])):
+                out.copy_(krylov[:n])
+                nrm[0] = 1.
+            f = scale / float(nrm[0]) if N > 1 else scale      # (N == 1: c_0 v_0, "only a phase", is not normalised again)
+            if f != 1.:
+                dev.check(L.tpa_scal(code, n, f, 0., out.data_ptr(), st), "scal")
+            return psif, N
+        out = dev.empty(n, np.complex128)
+        psif.dtype = np.dtype(np.complex128)
+        psif._skey = None
+        psif._arena = out
+        cz = np.ascontiguousarray(np.stack([c.real, c.imag], axis=1), dtype=np.float64)
+        dev.check(L.tpa_krylov_combine_z(code, n, krylov.data_ptr(), N, cz.ctypes.data, scale, out.data_ptr(), red, scr.data_ptr(),
+                                         nrm.ctypes.data, st), "krylov_combine_z")
+        if N == 1:            # only a phase: no division by the norm (reference :775)
+            return psif, N
+        if self._check_result_norm(float(nrm[0])):      # the start vector is the answer: v_0 with the coefficient 1
+            one = np.array([[1., 0.]])
+            dev.check(L.tpa_krylov_combine_z(code, n, krylov.data_ptr(), 1, one.ctypes.data, scale, out.data_ptr(), red, scr.data_ptr(),
+                                             nrm.ctypes.data, st), "krylov_combine_z")
+        elif nrm[0] != 1.:
+            dev.check(L.tpa_scal(dev.code(np.complex128), n, 1. / float(nrm[0]), 0., out.data_ptr(), st), "scal")
+        return psif, N
+
+    @staticmethod
+    def _check_result_norm(nrm):
+        """The ill-conditioned warning of ``_calc_result_full``; True = degenerate, the (normalised) start vector is the answer."""
+        if abs(1. - nrm) > 1.e-5:
+            stats['n_ill_conditioned'] += 1
+            logger.warning("poorly conditioned H matrix in KrylovBased! |psi_0| = %f", nrm)
+        if not (nrm > 1.e-8) or not np.isfinite(nrm):
+            stats['n_degenerate'] += 1
+            return True
+        return False
 
     def _calc_result_krylov(self, k):
         h, delta = self._h_krylov, self.delta

@@ -1,4 +1,4 @@
-"""Finite MPS of device-resident site tensors for the stand-alone drivers (``algorithms/dmrg.py``, ``algorithms/tebd.py``)
+"""Finite MPS of device-resident site tensors for the stand-alone drivers (``algorithms/dmrg.py``, ``tebd.py``, ``tdvp.py``)
 on boxes without TeNPy.  It holds what those two drivers touch -- ``from_product_state``, ``get_B`` / ``set_B`` /
 ``get_theta`` / ``set_SL`` / ``set_SR`` with the reference's leg labels ``('vL', 'p', 'vR')`` and canonical-form convention
 ``B = S**nuL  Gamma  S**nuR`` ('A' = (1,0), 'B' = (0,1), 'Th' = (1,1)), ``expectation_value``, ``entanglement_entropy``.
@@ -85,7 +85,10 @@ class MPS:
         return B
 
     def get_theta(self, i, n=2, formL=1., formR=1.):
-        """Two-site wave function with labels ``'vL', 'p0', 'p1', 'vR'`` (reference mps.py:3041)."""
+        """Wave function of ``n`` sites: ``n=2`` labels ``'vL', 'p0', 'p1', 'vR'``, ``n=1`` labels ``'vL', 'p0', 'vR'`` (reference
+        mps.py:3041)."""
+        if n == 1:
+            return self.get_B(i, (formL, formR)).replace_label('p', 'p0')
         assert n == 2
         i1 = i + 1
         B0 = self._scaled(self._B[i], self._S[i], formL - self.form[i][0], 'vL')
