@@ -46,8 +46,20 @@ const char *tpa_last_error(void);
  *          A_l(i,kk) = Abase[a_off + i*a_rs + kk*a_ks], B_l(kk,j) = Bbase[b_off + kk*b_ks + j*b_ns]
  *          (one of a_rs/a_ks and one of b_ks/b_ns should be 1 for coalescing; any strides are legal)
  *          flags bit0: conj(A), bit1: conj(B)   (complex only)
- * tasks  : int64[n_tasks][8]  = {c_off, m, n, ldc, link_begin, link_count, accumulate, 0}
- * tiles  : int32[n_tiles][4]  = {task, tile_row, tile_col, 0}   (tile shape: tpa_gemm_tile_shape(dtype, cfg))
+ *          links with k <= 0 are skipped wherever they stand in a chain; a chain without a non-empty link gives C_t = 0
+ *          (accumulate = 0) or leaves C_t as it is (accumulate = 1).  Real data ignores the flags.
+ * tasks  : int64[n_tasks][8]  = {c_off, m, n, ldc, link_begin, link_count, accumulate, act}
+ * tiles  : int32[n_tiles][4]  = {task, tile_row, tile_col, w}   (tile shape: tpa_gemm_tile_shape(dtype, cfg))
+ *          Every task is covered by its tiles exactly once, in any order.  Only the m x n elements of a block are written: the
+ *          ldc - n elements behind a row and everything between the blocks keep their contents.
+ * Identity-row skip (act, w; every caller but the block SVD leaves both 0).  `act` is 0 or the address of int32 words in DEVICE
+ *          memory; a tile with w > 0 of a task with act != 0 looks at ((const int32_t *)act)[w - 1].  A word of 0 is the caller's
+ *          promise that the rows of A which this tile needs are unit vectors, A(i, kk) = (i == kk) for the rows i of the tile (the
+ *          rows of the accumulated rotation Qtot of a block-Jacobi sweep that did not rotate: tpa_svd.hip, [W | G] <- Qtot [W | G]).
+ *          The tile of C is then a COPY of the rows of B: C(i, j) = B_l(i, j) of the FIRST link l = link_begin of the chain --
+ *          bit for bit what the product gives, because sums of exact zeros and one exact 1 * b do not round.  The copy does not
+ *          look at `accumulate`, at flags bit1 or at further links: the skip is for tasks with accumulate = 0 whose chain is that
+ *          one link (with k >= m; later links empty) without conj(B).  A non-zero word, w = 0 or act = 0 mean the ordinary product.
  * cfg    : 0 = large tiles (128 x 128 real), 1 = small tiles (64 x 64 real) -- chosen per plan by the host
  *          so that the launch has enough workgroups for 256 CUs.
  * All three tables live on the DEVICE (uploaded once per cached contraction plan).
@@ -62,7 +74,10 @@ int tpa_gemm_chain(int dtype, int cfg, const int64_t *tasks_dev, const int64_t *
  * `n` counts elements of dtype.  Scalars alpha are passed as (re, im); im ignored for F64.
  * Reductions are deterministic two-pass (per-workgroup partials, then one workgroup);
  * `scratch_dev` must hold >= TPA_RED_SCRATCH doubles; the result (2 doubles: re, im) is
- * written to out_dev[0..1] on the stream (no host sync).
+ * written to out_dev[0..1] on the stream (no host sync); two identical calls give bit-identical results.
+ * n <= 0: tpa_axpy and tpa_scal return 0 without a launch.  tpa_dot, tpa_nrm2sq and tpa_lanczos_update read and write no vector
+ * element and post out_dev[0..1] = (0, 0); tpa_lanczos_step posts ab_out[0..1] = (0, 0) and leaves w alone (as for any bsq = 0: no
+ * division).  tpa_krylov_combine / tpa_krylov_combine_z return TPA_E_BADARG.
  */
 #define TPA_RED_SCRATCH 4096
 int tpa_axpy(int dtype, int64_t n, double alpha_re, double alpha_im, const void *x_dev,
@@ -133,6 +148,9 @@ int tpa_krylov_combine_z(int basis_dtype, int64_t n, const void *krylov_dev, int
  *        {dst_off, src_off, ndim, flags, shape[MAXDIM], dst_stride[MAXDIM], src_stride[MAXDIM]}
  *        flags bit0: conjugate while copying (complex only).
  * The last dim is the fastest-varying loop index; strides in elements.
+ * All batched entry points of this section take one job per blockIdx.y: n_jobs <= 0 returns 0 without a launch, n_jobs > 65535
+ * returns TPA_E_BADARG before anything is launched.  `max_job_elems` is the largest element count of a job; it sizes the grid, which
+ * is capped at 512 workgroups per job (larger jobs loop).  Jobs with a zero extent are legal and do nothing.
  */
 #define TPA_COPY_MAXDIM 6
 int tpa_copy_batch(int dtype, const int64_t *jobs_dev, int n_jobs, int64_t max_job_elems,

@@ -259,6 +259,8 @@ class MockLib:
         return 0
 
     def tpa_krylov_combine(self, code, n, krylov_p, N, coeff_p, out_p, red_p, scr_p, norm_p, stream):
+        if n <= 0 or not 1 <= N <= 64:      # (TPA_ARG_CHECK of the entry point: before any device work)
+            return _lib.E_BADARG
         dt = _npdt(code)
         coeff = _host(coeff_p, (N,), np.float64)
         V = REG.view(krylov_p, dt)
@@ -271,6 +273,8 @@ class MockLib:
         return 0
 
     def tpa_copy_batch(self, code, jobs_p, n_jobs, max_elems, src_p, dst_p, stream):
+        if n_jobs <= 0 or n_jobs > 65535:      # one job per blockIdx.y: the grid limit is an argument error
+            return 0 if n_jobs <= 0 else _lib.E_BADARG
         dt = _npdt(code)
         W = 4 + 3 * MAXD
         jobs = REG.view(jobs_p, np.int64)[:W * n_jobs].reshape(n_jobs, W)
@@ -292,6 +296,8 @@ class MockLib:
         return 0
 
     def tpa_lincomb_batch(self, code, jobs_p, n_jobs, terms_p, max_elems, src_p, dst_p, stream):
+        if n_jobs <= 0 or n_jobs > 65535:      # one job per blockIdx.y: the grid limit is an argument error
+            return 0 if n_jobs <= 0 else _lib.E_BADARG
         dt = _npdt(code)
         jobs = REG.view(jobs_p, np.int64)[:8 * n_jobs].reshape(n_jobs, 8)
         n_terms = int(np.max(jobs[:, 4] + jobs[:, 5])) if n_jobs else 0
@@ -310,6 +316,8 @@ class MockLib:
         return 0
 
     def tpa_tri_lower_batch(self, code, jobs_p, n_jobs, max_elems, g_p, stream):
+        if n_jobs <= 0 or n_jobs > 65535:      # one job per blockIdx.y: the grid limit is an argument error
+            return 0 if n_jobs <= 0 else _lib.E_BADARG
         dt = _npdt(code)
         jobs = REG.view(jobs_p, np.int64)[:2 * n_jobs].reshape(n_jobs, 2)
         g = REG.view(g_p, dt)
@@ -321,6 +329,8 @@ class MockLib:
         return 0
 
     def tpa_scale_axis_batch(self, code, jobs_p, n_jobs, max_elems, x_p, s_p, s_cplx, stream):
+        if n_jobs <= 0 or n_jobs > 65535:      # one job per blockIdx.y: the grid limit is an argument error
+            return 0 if n_jobs <= 0 else _lib.E_BADARG
         dt = _npdt(code)
         jobs = REG.view(jobs_p, np.int64)[:6 * n_jobs].reshape(n_jobs, 6)
         x = REG.view(x_p, dt)
@@ -331,6 +341,8 @@ class MockLib:
         return 0
 
     def tpa_gather_axis_batch(self, code, jobs_p, n_jobs, max_elems, idx_p, src_p, dst_p, stream):
+        if n_jobs <= 0 or n_jobs > 65535:      # one job per blockIdx.y: the grid limit is an argument error
+            return 0 if n_jobs <= 0 else _lib.E_BADARG
         dt = _npdt(code)
         jobs = REG.view(jobs_p, np.int64)[:8 * n_jobs].reshape(n_jobs, 8)
         idx = REG.view(idx_p, np.int64)

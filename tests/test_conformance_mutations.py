@@ -1,0 +1,215 @@
+"""Sensitivity of the conformance suite: the numpy emulation is wrapped with ONE deliberate defect at a time and the checkers of
+tests/test_conformance_gemm.py, test_conformance_vec.py and test_conformance_copy.py have to reject every one of them (and accept the
+unbroken emulation on the same cases).  Needs no GPU: this is the evidence that a subtly wrong kernel would not pass."""
+import itertools
+
+import numpy as np
+import pytest
+
+import conformance_gemm_cases as cg
+import mock_device
+import test_conformance_copy as tc
+import test_conformance_vec as tv
+from tenpy_amd.linalg import _device as dev
+
+GEMM_CASE_STEP = 3         # every third case of the pairwise design of one real and one complex instantiation
+
+
+class Mutant:
+    """The emulation with some entry points replaced."""
+
+    def __init__(self, base, **entry_points):
+        self.base = base
+        self.__dict__.update(entry_points)
+
+    def __getattr__(self, name):
+        return getattr(self.base, name)
+
+
+def _table(ptr, dtype, width):
+    return mock_device.REG.view(ptr, dtype).reshape(-1, width).copy()
+
+
+# ---- defects of tpa_gemm_chain: (code, cfg, tasks, links, tiles, n_tiles, A, B, C, stream) ----------------------------------
+
+def _gemm_with_tables(edit):
+    """A defect that is a change of the tables the kernel sees."""
+    def make(base, case):
+        def gemm(code, cfg, tasks_p, links_p, tiles_p, n_tiles, A_p, B_p, C_p, stream):
+            tasks, links = _table(tasks_p, np.int64, 8), _table(links_p, np.int64, 8)
+            edit(tasks, links)
+            td, ld = dev.to_device(tasks), dev.to_device(links)
+            return base.tpa_gemm_chain(code, cfg, td.data_ptr(), ld.data_ptr(), tiles_p, n_tiles, A_p, B_p, C_p, stream)
+        return Mutant(base, tpa_gemm_chain=gemm)
+    return make
+
+
+def _gemm_with_output(edit):
+    """A defect that shows in C after a correct product: edit(case, tasks, C before, C after [writable view])."""
+    def make(base, case):
+        def gemm(code, cfg, tasks_p, links_p, tiles_p, n_tiles, A_p, B_p, C_p, stream):
+            dt = np.complex128 if code else np.float64
+            C = mock_device.REG.view(C_p, dt)
+            before = C.copy()
+            rc = base.tpa_gemm_chain(code, cfg, tasks_p, links_p, tiles_p, n_tiles, A_p, B_p, C_p, stream)
+            edit(case, _table(tasks_p, np.int64, 8), before, C)
+            return rc
+        return Mutant(base, tpa_gemm_chain=gemm)
+    return make
+
+
+def _conj_b_ignored(tasks, links):
+    links[:, 7] &= ~2
+
+
+def _last_k_dropped(tasks, links):
+    links[:, 2] -= (links[:, 2] % 16 != 0) & (links[:, 2] > 0)
+
+
+def _accumulate_ignored(tasks, links):
+    tasks[:, 6] = 0
+
+
+def _empty_middle_link_ends_chain(tasks, links):
+    for t in tasks:
+        ks = links[t[4]:t[4] + t[5], 2]
+        nonempty = np.flatnonzero(ks > 0)
+        if len(nonempty):
+            stop = [i for i in np.flatnonzero(ks == 0) if i > nonempty[0]]
+            if stop:
+                t[5] = stop[0]
+
+
+def _row_63_not_written(case, tasks, before, C):
+    for c_off, m, n, ldc in tasks[:, :4]:
+        if m >= 64:
+            C[c_off + 63 * ldc:c_off + 63 * ldc + n] = before[c_off + 63 * ldc:c_off + 63 * ldc + n]
+
+
+def _one_element_off_by_16_bounds(case, tasks, before, C):
+    lim = np.where(cg.reference(case)['mask'], cg.bound(case), 0)
+    i = int(np.argmax(lim))
+    C[i] += 16 * float(lim[i])
+
+
+def _write_into_ldc_padding(case, tasks, before, C):
+    c_off, m, n, ldc = tasks[0, :4]
+    C[c_off + (m - 1) * ldc + n] = 0.0
+
+
+GEMM_DEFECTS = {
+    'conj_b_ignored': _gemm_with_tables(_conj_b_ignored),
+    'last_k_of_partial_k_tiles_dropped': _gemm_with_tables(_last_k_dropped),
+    'last_row_of_a_64_row_tile_not_written': _gemm_with_output(_row_63_not_written),
+    'accumulate_ignored': _gemm_with_tables(_accumulate_ignored),
+    'empty_middle_link_ends_the_chain': _gemm_with_tables(_empty_middle_link_ends_chain),
+    'one_element_off_by_16_bounds': _gemm_with_output(_one_element_off_by_16_bounds),
+    'one_write_into_the_ldc_padding': _gemm_with_output(_write_into_ldc_padding),
+}
+
+_gemm_cases = {}
+
+
+def gemm_cases():
+    if not _gemm_cases:
+        for inst in ('chain_64x64x1x2_real_cfg1', 'chain_64x32x2x1_complex_cfg1'):
+            _gemm_cases[inst] = list(itertools.islice(cg.small_cases(inst), 0, None, GEMM_CASE_STEP))
+    return [c for cases in _gemm_cases.values() for c in cases]
+
+
+def _rejected(check, *args):
+    try:
+        check(*args)
+    except AssertionError:
+        return True
+    return False
+
+
+def _gemm_rejections(make, base):
+    return sum(_rejected(lambda c: cg.check_case(c, cg.run_case(c, L=make(base, c))), c) for c in gemm_cases())
+
+
+# ---- defects of the vector and copy entry points ----------------------------------------------------------------------------
+
+def _dot_drops_last(base):
+    return Mutant(base, tpa_dot=lambda code, n, x, y, cj, out, scr, st: base.tpa_dot(code, n - 1, x, y, cj, out, scr, st))
+
+
+def _copy_conj_ignored(base):
+    def call(code, jobs_p, n_jobs, max_elems, src_p, dst_p, stream):
+        jobs = _table(jobs_p, np.int64, 4 + 3 * tc.MAXD)
+        jobs[:, 3] = 0
+        jd = dev.to_device(jobs)
+        return base.tpa_copy_batch(code, jd.data_ptr(), n_jobs, max_elems, src_p, dst_p, stream)
+    return Mutant(base, tpa_copy_batch=call)
+
+
+def _gather_idx_off_ignored(base):
+    """(Flat addressing like the kernel's: an index that belongs to another job may point beyond this job's source block.)"""
+    def call(code, jobs_p, n_jobs, max_elems, idx_p, src_p, dst_p, stream):
+        dt = np.complex128 if code else np.float64
+        idx, src, dst = mock_device.REG.view(idx_p, np.int64), mock_device.REG.view(src_p, dt), mock_device.REG.view(dst_p, dt)
+        for d_off, s_off, pre, ls, ld, post, i_off, _ in _table(jobs_p, np.int64, 8)[:n_jobs]:
+            i, j, l = np.indices((pre, ld, post)).reshape(3, -1)
+            dst[d_off + (i * ld + j) * post + l] = src[np.minimum(s_off + (i * ls + idx[0 + j]) * post + l, len(src) - 1)]
+        return 0
+    return Mutant(base, tpa_gather_axis_batch=call)
+
+
+def _tri_diagonal_not_halved(base):
+    def call(code, jobs_p, n_jobs, max_elems, g_p, stream):
+        rc = base.tpa_tri_lower_batch(code, jobs_p, n_jobs, max_elems, g_p, stream)
+        g = mock_device.REG.view(g_p, np.complex128 if code else np.float64)
+        for g_off, n in _table(jobs_p, np.int64, 2)[:n_jobs]:
+            g[g_off + np.arange(n) * (n + 1)] *= 2          # (G_ii - 1) instead of (G_ii - 1) / 2
+        return rc
+    return Mutant(base, tpa_tri_lower_batch=call)
+
+
+def _vec_copy_probes():
+    """name -> (make mutant, [probe(L) that raises AssertionError when the checker rejects the library L])"""
+    rng = np.random.default_rng(12)
+    probes = {}
+    dots = [(tv._vec(rng, n, cplx), tv._vec(rng, n, cplx), cj) for n in (2, 65, 2049) for cplx in (False, True) for cj in (0, 1)]
+    probes['tpa_dot_drops_its_last_element'] = (_dot_drops_last, [
+        (lambda L, a=a: tv.check_dot(a[0], a[1], a[2], tv.run_dot(a[0], a[1], a[2], L=L))) for a in dots])
+    copies = [tc.copy_case(np.random.default_rng([13, b]), True, batch) for b, batch in enumerate(('one_element', 'forty_jobs'))]
+    copies[0].jobs[:, 3] = 1
+    probes['copy_conjugation_flag_ignored'] = (_copy_conj_ignored, [
+        (lambda L, c=c: tc.check_copy(c, tc.run_copy(c, L=L))) for c in copies])
+    gathers = [tc.gather_case(np.random.default_rng([14, int(cplx)]), cplx, 'forty_jobs') for cplx in (False, True)]
+    probes['gather_idx_off_ignored'] = (_gather_idx_off_ignored, [
+        (lambda L, c=c: tc.check_gather(c, tc.run_gather(c, L=L))) for c in gathers])
+    tris = [tc.tri_case(np.random.default_rng([15, int(cplx)]), cplx, [1, 5, 64]) for cplx in (False, True)]
+    probes['tri_lower_diagonal_not_halved'] = (_tri_diagonal_not_halved, [
+        (lambda L, c=c: tc.check_tri(c, tc.run_tri(c, L=L))) for c in tris])
+    return probes
+
+
+DEFECTS = list(GEMM_DEFECTS) + ['tpa_dot_drops_its_last_element', 'copy_conjugation_flag_ignored', 'gather_idx_off_ignored',
+                                'tri_lower_diagonal_not_halved']
+
+
+def test_defect_list_is_complete():
+    assert len(DEFECTS) == 11 and set(DEFECTS) == set(GEMM_DEFECTS) | set(_vec_copy_probes())
+
+
+def test_unbroken_emulation_is_accepted(monkeypatch):
+    base = mock_device.install(monkeypatch)
+    assert _gemm_rejections(lambda b, c: b, base) == 0
+    for make, probes in _vec_copy_probes().values():
+        for probe in probes:
+            probe(base)
+
+
+@pytest.mark.parametrize("defect", DEFECTS)
+def test_conformance_detects_mutations(monkeypatch, defect):
+    base = mock_device.install(monkeypatch)
+    if defect in GEMM_DEFECTS:
+        n = _gemm_rejections(GEMM_DEFECTS[defect], base)
+        print("MUTATION %s: rejected by %d of %d GEMM cases" % (defect, n, len(gemm_cases())))
+    else:
+        make, probes = _vec_copy_probes()[defect]
+        n = sum(_rejected(probe, make(base)) for probe in probes)
+        print("MUTATION %s: rejected by %d of %d probes" % (defect, n, len(probes)))
+    assert n >= 1, "the conformance checker accepts an emulation with the defect '%s'" % defect
