@@ -28,7 +28,7 @@ struct QlaPanelSmem {
 };
 union QlaSmem {
     QlaPanelSmem p;
-    WySmem<PNB, NTQ> u;
+    WySmem<double, PNB, NTQ> u;
 };
 
 // k: first column of the panel whose reflectors are APPLIED in this launch (k < 0: none yet -- the very first launch only factorises
@@ -53,8 +53,8 @@ __global__ __launch_bounds__(NTQ) void qr_la_step_kernel(const QrpJob *__restric
         const int64_t jl = j0 + (tid & (RCOLS - 1));
         const bool col_ok = (jl < N) && (jl >= (int64_t)k + 2 * PNB);
         if (__ballot(col_ok) == 0) return;      // the same 16 columns in every wavefront: uniform over the workgroup
-        if (tid < PNB * PNB) sm.u.T[tid / PNB][tid % PNB] = Tpan2[((int64_t)((k / PNB) & 1) * n_jobs + b) * PNB * PNB + tid];
-        wy_apply_tile<PNB, true, false, NTQ>(Xb, 1, M, k, M, j0, N, Vall + J.x_off + (int64_t)k * M, nbk, 0, sm.u, col_ok);
+        if (tid < PNB * PNB) sm.u.Tf[tid / PNB][tid % PNB] = Tpan2[((int64_t)((k / PNB) & 1) * n_jobs + b) * PNB * PNB + tid];
+        wy_apply_tile<double, PNB, true, false, NTQ>(Xb, 1, M, k, M, j0, N, Vall + J.x_off + (int64_t)k * M, nbk, 0, sm.u, col_ok);
         return;
     }
     // -------------------------------------------------------------------- panel role: columns kp .. kp + nb - 1

@@ -22,6 +22,7 @@
 #include <memory>
 #include <numeric>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -1481,1161 +1482,9 @@ __global__ __launch_bounds__(NT) void svd_finish_kernel(const SvdJob *__restrict
     }
 }
 
-// ===================================================================================================
-// Rank-revealing preconditioner: Householder QR with column pivoting (BLAS-2, batched over the charge blocks).
-//
-// DMRG wave-function blocks are numerically rank deficient (rank <= chi of d*chi; measured sigma from 1 down
-// to 1e-27 with a cliff) and strongly graded.  Plain one-sided Jacobi then needs ~25 sweeps over ALL rows.
-// With X P = Q [R; 0] (X = A or A^T, tall M x N) the Jacobi iteration only has to diagonalise the r x N factor
-// R (r = numerical rank): ~7 sweeps over ~half the rows (numpy experiment on real theta blocks: 25 -> 7 sweeps).
-//     X = (Q_r U_R) Sigma (VH_R P^T),   SVD(R) = U_R Sigma VH_R  by the block-Jacobi kernels above.
-// Per step k two launches for all blocks together: `qrp_pivot_kernel` (one workgroup per block: pivot search on
-// the exact residual column norms, column swap, Householder vector; X is kept column-major so that this is coalesced) and `qrp_update_kernel` (column tiles: rank-1
-// update of the trailing matrix and exact recomputation of the residual norms in the same pass).
-struct QrpJob {  // int64[8]
-    int64_t x_off, M, N, c_off, tr, r_off, pad0, pad1;   // c_off: offset into cn / tau / cperm ; tr: X = A^T
-};
-struct QrpState {  // per job
-    int rank, done, nbk, last;   // nbk: size of the current panel; last: that panel was the final one
-};
-
-__global__ __launch_bounds__(NT) void qrp_init_kernel(const QrpJob *__restrict__ jobs, const SvdJob *__restrict__ sj,
-                                                      const double *__restrict__ A, double *__restrict__ X,
-                                                      double *__restrict__ cn, int64_t *__restrict__ cperm,
-                                                      QrpState *__restrict__ state) {
-    // grid (column tiles of 64, jobs): X = A or A^T stored COLUMN-major (X[j*M + i]), exact column norms^2,
-    // identity permutation.  Wave w owns the columns j0 + 16 w .. +15 of the tile, lanes run along the rows
-    // (contiguous in X); for X = A the 64 x 64 tile is transposed through LDS so that both sides stay coalesced.
-    __shared__ double tile[64][65];
-    const QrpJob J = jobs[blockIdx.y];
-    const SvdJob S = sj[blockIdx.y];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t j0 = (int64_t)blockIdx.x * 64;
-    if (j0 >= J.N) return;
-    double acc[16];
-#pragma unroll
-    for (int rr = 0; rr < 16; ++rr) acc[rr] = 0.0;
-    for (int64_t i0 = 0; i0 < J.M; i0 += 64) {
-        if (!J.tr) {
-            __syncthreads();
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) {
-                const int64_t i = i0 + wave * 16 + rr, j = j0 + lane;
-                tile[wave * 16 + rr][lane] = (i < J.M && j < J.N) ? A[S.a_off + i * S.n + j] : 0.0;
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-            const int64_t j = j0 + wave * 16 + rr, i = i0 + lane;
-            if (j < J.N && i < J.M) {
-                const double v = J.tr ? A[S.a_off + j * S.n + i] : tile[lane][wave * 16 + rr];
-                X[J.x_off + j * J.M + i] = v;
-                acc[rr] = fma(v, v, acc[rr]);
-            }
-        }
-    }
-#pragma unroll
-    for (int rr = 0; rr < 16; ++rr) {
-        const double t = wave_sum(acc[rr]);
-        const int64_t j = j0 + wave * 16 + rr;
-        if (lane == 0 && j < J.N) {
-            cn[J.c_off + j] = t;
-            cperm[J.c_off + j] = j;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) state[blockIdx.y] = QrpState{0, 0, 0, 0};
-}
-
-constexpr int NTP_MAX = 256;   // threads of the panel kernel: 64 (one wavefront, no cross-wave barriers) or 256
-constexpr int PNB = 8;    // pivot columns factorised per launch (panel pivoting: the PNB largest residual columns)
-constexpr int RPT_MAX = 32;  // rows / candidate columns per thread held in registers (template RPT = 8, 16, 32)  ->  max(m, n) <= 8192
-
-// sum the values v[q], q < n or q == extra, over the workgroup (NTP threads); results valid in every thread.  The callers
-// sit in fully unrolled loops, so n / extra are constants after unrolling and the unused entries cost nothing.
-template <int NTP, int K>
-__device__ __forceinline__ void block_sum_vec(double (&v)[K], double (*red)[PNB + 1], int n, int extra) {
-#pragma unroll
-    for (int q = 0; q < K; ++q)
-        if (q < n || q == extra) v[q] = wave_sum(v[q]);
-    if (NTP == 64) return;   // a single wavefront: wave_sum already left the total in every lane
-    lds_barrier();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < K; ++q)
-            if (q < n || q == extra) red[threadIdx.x >> 6][q] = v[q];
-    }
-    lds_barrier();
-#pragma unroll
-    for (int q = 0; q < K; ++q)
-        if (q < n || q == extra) {
-            double t = 0;
-#pragma unroll
-            for (int w = 0; w < NTP / 64; ++w) t += red[w][q];
-            v[q] = t;
-        }
-}
-
-// One workgroup per block: pick the (up to) PNB unprocessed columns with the largest residual norms and factorise
-// that panel (Householder vectors -> Vall, R entries -> X, compact-WY factor -> Tpan).  Columns are never moved:
-// cperm[k + l] records which physical column became logical column k + l, cn[j] = -1 marks column j as done, and the
-// trailing update walks over the physical columns skipping the marked ones.  Greedy pivoting is exact for the first
-// column of a panel and by pre-panel norms for the others; the rank decision is unaffected because the trailing update
-// recomputes every residual norm exactly.
-// (A one-wavefront variant with the whole panel in the registers of one SIMD was 1.6x slower: the per-lane serial work
-// outweighs the saved barriers.)
-template <int NTP, int RPT>
-__global__ __launch_bounds__(NTP) void qrp_panel_kernel(const QrpJob *__restrict__ jobs, int k, double *__restrict__ X,
-                                                       double *__restrict__ Vall, double *__restrict__ cn,
-                                                       double *__restrict__ tau, int64_t *__restrict__ cperm,
-                                                       QrpState *__restrict__ state, const double *__restrict__ fro2,
-                                                       double tol2, double *__restrict__ Tpan, int pivot) {
-    __shared__ double rv[2 * (NTP / 64)];
-    __shared__ int64_t ri[2 * (NTP / 64)];
-    __shared__ double red[NTP / 64][PNB + 1];
-    __shared__ int64_t s_p[PNB];
-    __shared__ int s_nbk;
-    __shared__ double s_alpha, s_vrow[PNB], Tf[PNB][PNB];
-    const int b = blockIdx.x;
-    const QrpJob J = jobs[b];
-    const QrpState st0 = state[b];
-    if (st0.done) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t M = J.M, N = J.N;
-    const int64_t Kmax = (M < N) ? M : N;      // number of reflectors (N <= M in the pivoted use)
-    if (st0.last || k >= Kmax) {
-        if (tid == 0) state[b] = QrpState{st0.last ? st0.rank : (int)Kmax, 1, 0, 0};
-        return;
-    }
-    // ---- the PNB largest residual norms among the unprocessed columns (ties -> smallest index: deterministic)
-    double cand[RPT];
-#pragma unroll
-    for (int t = 0; t < RPT; ++t) {
-        const int64_t j = tid + (int64_t)t * NTP;
-        cand[t] = (j < N) ? cn[J.c_off + j] : -4.0;       // processed columns hold -1
-    }
-    const double thresh = tol2 * fro2[b];
-    if (tid == 0) s_nbk = 0;
-    if (!pivot) {   // plain QR: the next PNB columns in their natural order, no rank test
-        if (tid == 0) {
-            const int nb_ = (int)((Kmax - k < PNB) ? (Kmax - k) : PNB);
-            for (int l = 0; l < nb_; ++l) s_p[l] = (int64_t)k + l;
-            s_nbk = nb_;
-        }
-        lds_barrier();
-    } else {
-        // One barrier per pivot: every wavefront finds its best candidate (value by wave_max, smallest index among equal values
-        // by wave_min), publishes it in a double-buffered LDS slot, and EVERY thread merges the NTP/64 entries itself.
-        int nsel = 0;
-        for (int l = 0; l < PNB; ++l) {
-            double bv = -3.0;
-            int bidx = 0x7fffffff;
-#pragma unroll
-            for (int t = 0; t < RPT; ++t)
-                if (cand[t] > bv) {
-                    bv = cand[t];
-                    bidx = tid + t * NTP;
-                }
-            const double wv = wave_max(bv);
-            const int wi = wave_min((bv == wv) ? bidx : 0x7fffffff);
-            if (lane == 0) {
-                rv[(l & 1) * (NTP / 64) + wave] = wv;
-                ri[(l & 1) * (NTP / 64) + wave] = wi;
-            }
-            lds_barrier();
-            double v0 = rv[(l & 1) * (NTP / 64)];
-            int64_t i0 = ri[(l & 1) * (NTP / 64)];
-#pragma unroll
-            for (int w = 1; w < NTP / 64; ++w) {
-                const double vw = rv[(l & 1) * (NTP / 64) + w];
-                const int64_t iw = ri[(l & 1) * (NTP / 64) + w];
-                if (vw > v0 || (vw == v0 && iw < i0)) {
-                    v0 = vw;
-                    i0 = iw;
-                }
-            }
-            if (!(v0 > thresh)) break;   // uniform: every thread merged the same entries
-            if (tid == 0) s_p[l] = i0;
-            nsel = l + 1;
-#pragma unroll
-            for (int t = 0; t < RPT; ++t)
-                if (tid + t * NTP == (int)i0) cand[t] = -4.0;
-        }
-        if (tid == 0) s_nbk = nsel;
-        lds_barrier();
-    }
-    const int nbk = s_nbk;
-    if (nbk == 0) {
-        if (tid == 0) state[b] = QrpState{k, 1, 0, 0};
-        return;
-    }
-    if (tid == 0) {
-        const bool last = (nbk < PNB);
-        state[b] = QrpState{last ? k + nbk : 0, 0, nbk, last ? 1 : 0};
-        for (int x = 0; x < PNB; ++x)
-            for (int y = 0; y < PNB; ++y) Tf[x][y] = 0.0;
-    }
-    if (tid < nbk) {
-        cperm[J.c_off + k + tid] = s_p[tid];
-        cn[J.c_off + s_p[tid]] = -1.0;     // processed
-    }
-    lds_barrier();
-    double *Xb = X + J.x_off;
-    // ---- gather the panel into registers (X is column-major: contiguous loads)
-    double c[PNB][RPT];
-#pragma unroll
-    for (int t = 0; t < RPT; ++t) {
-        const int64_t i = tid + (int64_t)t * NTP;
-#pragma unroll
-        for (int l = 0; l < PNB; ++l) c[l][t] = (i < M && l < nbk) ? Xb[s_p[l] * M + i] : 0.0;
-    }
-    // ---- factorise the panel, column by column (must be fully unrolled: c[l] has to stay in registers)
-#pragma clang loop unroll(full)
-    for (int l = 0; l < PNB; ++l) {
-        if (l < nbk) {   // uniform
-            const int64_t kl = (int64_t)k + l;
-            if (l > 0) {
-                // c_l <- (I - V Tf^T V^T) c_l  with the l reflectors found so far (their vectors sit in c[0..l-1])
-                double y[PNB];
-#pragma unroll
-                for (int m = 0; m < PNB; ++m) {
-                    y[m] = 0.0;
-                    if (m < l) {
-#pragma unroll
-                        for (int t = 0; t < RPT; ++t) y[m] = fma(c[m][t], c[l][t], y[m]);
-                    }
-                }
-                block_sum_vec<NTP, PNB>(y, red, l, -1);
-                double z[PNB];
-#pragma unroll
-                for (int m = 0; m < PNB; ++m) {
-                    z[m] = 0.0;
-                    if (m < l) {
-#pragma unroll
-                        for (int mm = 0; mm < PNB; ++mm)
-                            if (mm <= m) z[m] = fma(Tf[mm][m], y[mm], z[m]);
-                    }
-                }
-#pragma unroll
-                for (int m = 0; m < PNB; ++m)
-                    if (m < l) {
-#pragma unroll
-                        for (int t = 0; t < RPT; ++t) c[l][t] = fma(-c[m][t], z[m], c[l][t]);
-                    }
-            }
-            // norm below the diagonal and inner products with the earlier vectors (for Tf) in one reduction; the diagonal
-            // element alpha and row kl of the earlier vectors are broadcast through LDS by the thread that owns row kl
-            double g[PNB + 1];
-#pragma unroll
-            for (int q = 0; q <= PNB; ++q) g[q] = 0.0;
-#pragma unroll
-            for (int t = 0; t < RPT; ++t) {
-                const int64_t i = tid + (int64_t)t * NTP;
-                if (i > kl && i < M) {
-                    g[PNB] = fma(c[l][t], c[l][t], g[PNB]);
-#pragma unroll
-                    for (int m = 0; m < PNB; ++m)
-                        if (m < l) g[m] = fma(c[m][t], c[l][t], g[m]);
-                } else if (i == kl) {
-                    s_alpha = c[l][t];
-#pragma unroll
-                    for (int m = 0; m < PNB; ++m)
-                        if (m < l) s_vrow[m] = c[m][t];
-                }
-            }
-            block_sum_vec<NTP, PNB + 1>(g, red, l, PNB);
-            const double s2 = g[PNB], alpha = s_alpha;
-            // beta = -sign(alpha) |x|,  tau = (beta - alpha) / beta = 1 + |alpha| / |x|,  scale = 1 / (alpha - beta): one reciprocal
-            // square root and one reciprocal, both from the hardware seed + Newton steps (~1 ulp; a Householder vector does not need
-            // correctly rounded divisions, and these sit on the serial path of every column)
-            double beta = alpha, tk = 0.0, scale = 0.0;
-            if (s2 > 0.0) {
-                const double x2 = fma(alpha, alpha, s2);
-                double r = __builtin_amdgcn_rsq(x2);
-                r = r * fma(-0.5 * x2 * r, r, 1.5);
-                r = r * fma(-0.5 * x2 * r, r, 1.5);          // 1 / |x|
-                const double nx = x2 * r;                   // |x|
-                beta = -copysign(nx, alpha);
-                tk = fma(fabs(alpha), r, 1.0);
-                const double d = alpha - beta;              // = sign(alpha) (|alpha| + |x|): no cancellation
-                double q = __builtin_amdgcn_rcp(d);
-                q = q * fma(-d, q, 2.0);
-                scale = q * fma(-d, q, 2.0);
-            }
-            // column l of the compact-WY factor: Tf[i2][l] = -tau sum_{m=i2}^{l-1} Tf[i2][m] (v_m^T v_l), thread i2 each
-            if (tid < l) {
-                double acc = 0;
-#pragma unroll
-                for (int m = 0; m < PNB; ++m)
-                    if (m >= tid && m < l) acc = fma(Tf[tid][m], g[m] * scale + s_vrow[m], acc);
-                Tf[tid][l] = -tk * acc;
-            } else if (tid == l) {
-                Tf[l][l] = tk;
-                tau[J.c_off + kl] = tk;
-            }
-            double *vk = Vall + J.x_off + kl * M;
-            double *xc = Xb + s_p[l] * M;
-#pragma unroll
-            for (int t = 0; t < RPT; ++t) {
-                const int64_t i = tid + (int64_t)t * NTP;
-                if (i < M) {   // (selects, no divergent branches)
-                    const double cv = c[l][t];
-                    const double v = (i > kl) ? cv * scale : ((i == kl) ? 1.0 : 0.0);
-                    xc[i] = (i < kl) ? cv : ((i == kl) ? beta : 0.0);   // R entry (rows k .. kl-1 were changed by this panel's earlier reflectors)
-                    vk[i] = v;
-                    c[l][t] = v;
-                }
-            }
-            lds_barrier();   // Tf column l, s_alpha / s_vrow reuse
-        }
-    }
-    if (tid < PNB * PNB) Tpan[(int64_t)b * PNB * PNB + tid] = Tf[tid / PNB][tid % PNB];
-}
-
-// ---- compact-WY block reflector applied to a 16-column tile of a row-major matrix, on the matrix cores ----------
-//     C[k0:, tile] <- (I - V Tf' V^T) C[k0:, tile],    Tf' = Tf^T (TRANS: trailing update of the factorisation)
-//                                                      or Tf (forming Q U_R),
-// V[l*M + i] = component i of reflector l (0 above its diagonal), nb <= NB reflectors, Tf upper triangular in LDS.
-// 1024 threads = 16 wavefronts, each owning 16-row slabs (slab s of wave w = rows k0 + 16 (w + 16 s) ...):
-//   pass 1  Y  = V^T C      v_mfma_f64_16x16x4: A(l, i) = V, B(i, j) = C, K runs over the rows      -> LDS reduce
-//   small   Z  = Tf' Y      (NB x 16, 256 threads)
-//   pass 2  C -= V Z        A(i, l) = V, B(l, j) = -Z, accumulator preloaded with the C slab (NB/4 MFMAs per slab)
-// Returns (NORMS) sum_{i >= kend} C[i, j]^2 of the updated tile column j = j0 + (lane & 15), valid in threads < 16.
-constexpr int NTR = 1024, RCOLS = 16;
-
-template <int NB, int NTH = NTR>
-struct WySmem {
-    double red[NTH / 64][NB][RCOLS];
-    double Y[NB][RCOLS], Z[NB][RCOLS], T[NB][NB];
-    double nrm[NTH / 64][RCOLS];
-};
-
-template <int NB, bool TRANS, bool NORMS, int NTH = NTR>
-__device__ __forceinline__ double wy_apply_tile(double *Cb, int64_t rs, int64_t cs, int64_t k0, int64_t M, int64_t j0, int64_t jend,
-                                                const double *__restrict__ V, int nb, int64_t kend, WySmem<NB, NTH> &sm,
-                                                bool col_ok = true) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lo = lane & 15, kq = lane >> 4;
-    const int64_t j = j0 + lo;
-    const bool jok = (j < jend) && col_ok;
-    // ---- pass 1: Y(l, j) = sum_i V(l, i) C(i, j)
-    d4 acc = {0, 0, 0, 0};
-    for (int64_t i0 = k0 + 16 * wave; i0 < M; i0 += 16 * (NTH / 64)) {
-        double a[4], bb[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t i = i0 + 4 * kq + q;
-            const bool iok = i < M;
-            a[q] = (iok && lo < nb) ? V[(int64_t)lo * M + i] : 0.0;
-            bb[q] = (iok && jok) ? Cb[i * rs + j * cs] : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q], bb[q], acc, 0, 0, 0);
-    }
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg)
-        if (kq + 4 * reg < NB) sm.red[wave][kq + 4 * reg][lo] = acc[reg];
-    __syncthreads();
-    if (threadIdx.x < NB * RCOLS) {
-        const int l = threadIdx.x >> 4, c = threadIdx.x & 15;
-        double t = 0;
-#pragma unroll
-        for (int q = 0; q < NTH / 64; ++q) t += sm.red[q][l][c];
-        sm.Y[l][c] = t;
-    }
-    __syncthreads();
-    if (threadIdx.x < NB * RCOLS) {
-        const int l = threadIdx.x >> 4, c = threadIdx.x & 15;
-        double t = 0;
-#pragma unroll
-        for (int m = 0; m < NB; ++m) t = fma(TRANS ? sm.T[m][l] : sm.T[l][m], sm.Y[m][c], t);
-        sm.Z[l][c] = -t;
-    }
-    __syncthreads();
-    double zneg[NB / 4];
-#pragma unroll
-    for (int q = 0; q < NB / 4; ++q) zneg[q] = sm.Z[4 * q + kq][lo];
-    // ---- pass 2: two 16-row slabs per iteration (all loads before the stores: the compiler cannot prove that the
-    //      stores of one slab do not alias the loads of the next)
-    double nrm = 0;
-    for (int64_t i0 = k0 + 16 * wave; i0 < M; i0 += 2 * 16 * (NTH / 64)) {
-        d4 c[2];
-        double av[2][NB / 4];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int64_t ib = i0 + (int64_t)h * 16 * (NTH / 64);
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int64_t i = ib + kq + 4 * reg;
-                c[h][reg] = (i < M && jok) ? Cb[i * rs + j * cs] : 0.0;
-            }
-#pragma unroll
-            for (int q = 0; q < NB / 4; ++q) {
-                const int64_t i = ib + lo;
-                const int l = 4 * q + kq;
-                av[h][q] = (i < M && l < nb) ? V[(int64_t)l * M + i] : 0.0;
-            }
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int q = 0; q < NB / 4; ++q) c[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[h][q], zneg[q], c[h], 0, 0, 0);
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int64_t ib = i0 + (int64_t)h * 16 * (NTH / 64);
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int64_t i = ib + kq + 4 * reg;
-                if (i < M && jok) {
-                    Cb[i * rs + j * cs] = c[h][reg];
-                    if (NORMS && i >= kend) nrm = fma(c[h][reg], c[h][reg], nrm);
-                }
-            }
-        }
-    }
-    if (!NORMS) return 0.0;
-    nrm += __shfl_xor(nrm, 16, 64);
-    nrm += __shfl_xor(nrm, 32, 64);
-    if (lane < RCOLS) sm.nrm[wave][lo] = nrm;
-    __syncthreads();
-    double t = 0;
-    if (threadIdx.x < RCOLS) {
-#pragma unroll
-        for (int q = 0; q < NTH / 64; ++q) t += sm.nrm[q][threadIdx.x];
-    }
-    return t;
-}
-
-// trailing update with the panel's nbk reflectors:  X[k:, j] <- (I - V Tf^T V^T) X[k:, j]  for every column j that has not
-// been factorised yet (cn[j] >= 0; tiles walk over the physical columns), plus the exact residual norms (rows >= k + nbk).
-__global__ __launch_bounds__(NTR) void qrp_update_kernel(const QrpJob *__restrict__ jobs, int k, double *__restrict__ X,
-                                                         const double *__restrict__ Vall, double *__restrict__ cn,
-                                                         const QrpState *__restrict__ state,
-                                                         const double *__restrict__ Tpan) {
-    __shared__ WySmem<PNB> sm;
-    const int b = blockIdx.y;
-    const QrpState st = state[b];
-    if (st.done || st.nbk == 0) return;
-    const QrpJob J = jobs[b];
-    const int nbk = st.nbk;
-    const int64_t j0 = (int64_t)blockIdx.x * RCOLS;
-    if (j0 >= J.N) return;
-    const int64_t jl = j0 + (threadIdx.x & (RCOLS - 1));
-    const bool col_ok = (jl < J.N) && (cn[J.c_off + jl] >= 0.0);
-    if (__ballot(col_ok) == 0) return;   // same 16 columns in every wavefront: uniform over the workgroup
-    if (threadIdx.x < PNB * PNB) sm.T[threadIdx.x / PNB][threadIdx.x % PNB] = Tpan[(int64_t)b * PNB * PNB + threadIdx.x];
-    const double nrm = wy_apply_tile<PNB, true, true>(X + J.x_off, 1, J.M, k, J.M, j0, J.N, Vall + J.x_off + (int64_t)k * J.M,
-                                                      nbk, (int64_t)k + nbk, sm, col_ok);
-    if (threadIdx.x < RCOLS && col_ok) cn[J.c_off + jl] = nrm;
-}
-
-// after the factorisation: the columns that were never used as pivots become the logical columns r .. N-1 (in
-// increasing physical order)
-__global__ __launch_bounds__(NT) void qrp_finish_perm_kernel(const QrpJob *__restrict__ jobs, const QrpState *__restrict__ state,
-                                                             const double *__restrict__ cn, int64_t *__restrict__ cperm) {
-    __shared__ int cnt[NT];
-    const QrpJob J = jobs[blockIdx.x];
-    const int64_t N = J.N, r = state[blockIdx.x].rank;
-    const int64_t per = (N + NT - 1) / NT, lo = (int64_t)threadIdx.x * per, hi = (lo + per < N) ? lo + per : N;
-    int mine = 0;
-    for (int64_t j = lo; j < hi; ++j) mine += (cn[J.c_off + j] >= 0.0) ? 1 : 0;
-    cnt[threadIdx.x] = mine;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int t = 0; t < NT; ++t) {
-            const int c = cnt[t];
-            cnt[t] = run;
-            run += c;
-        }
-    }
-    __syncthreads();
-    int64_t pos = r + cnt[threadIdx.x];
-    for (int64_t j = lo; j < hi; ++j)
-        if (cn[J.c_off + j] >= 0.0) cperm[J.c_off + pos++] = j;
-}
-
-// R_top (r x N, contiguous, logical column order) = upper-trapezoidal part of the first r rows of X
-__global__ __launch_bounds__(NT) void qrp_extract_kernel(const QrpJob *__restrict__ jobs, const QrpState *__restrict__ state,
-                                                         const double *__restrict__ X, const int64_t *__restrict__ cperm,
-                                                         double *__restrict__ Rtop) {
-    const QrpJob J = jobs[blockIdx.y];
-    const int64_t r = state[blockIdx.y].rank, N = J.N;
-    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < r * N; e += (int64_t)gridDim.x * NT) {
-        const int64_t i = e / N, j = e - i * N;
-        Rtop[J.r_off + e] = (j >= i) ? X[J.x_off + cperm[J.c_off + j] * J.M + i] : 0.0;
-    }
-}
-
-// T (M x r, row-major, stored at x_off) = [U_R ; 0]
-__global__ __launch_bounds__(NT) void qrp_form_t_kernel(const QrpJob *__restrict__ jobs, const QrpState *__restrict__ state,
-                                                        const double *__restrict__ UR, double *__restrict__ T) {
-    const QrpJob J = jobs[blockIdx.y];
-    const int64_t r = state[blockIdx.y].rank, M = J.M;
-    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < M * r; e += (int64_t)gridDim.x * NT) {
-        const int64_t i = e / r;
-        T[J.x_off + e] = (i < r) ? UR[J.r_off + e] : 0.0;
-    }
-}
-
-// ---- blocked application of Q_r = H_0 ... H_{r-1} (compact WY, 16 reflectors per launch) ------------------------
-// H_{k0} ... H_{k0+15} = I - V Tf V^T  with Tf upper triangular (LAPACK dlarft, forward / columnwise).
-constexpr int QNB = 16;
-
-// one workgroup per (block of 16 reflectors, job): Gram of the panel rows, then the Tf recurrence.  One launch
-// covers every block of every job.
-__global__ __launch_bounds__(NTR) void qrp_tfactor_kernel(const QrpJob *__restrict__ jobs, const QrpState *__restrict__ state,
-                                                          const double *__restrict__ Vall, const double *__restrict__ tau,
-                                                          double *__restrict__ Tfac) {
-    __shared__ double S[QNB][QNB + 1];
-    __shared__ double Tf[QNB][QNB + 1];
-    const QrpJob J = jobs[blockIdx.y];
-    const int64_t r = state[blockIdx.y].rank, M = J.M;
-    const int64_t k0 = (int64_t)blockIdx.x * QNB;
-    if (k0 >= r) return;
-    const int nb = (int)((r - k0 < QNB) ? (r - k0) : QNB);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const double *V = Vall + J.x_off + k0 * M;
-    // 16 waves x 16 (l, l') pairs each: pair index = wave * 16 + q  ->  l = wave, l' = q
-    for (int q = 0; q < QNB; ++q) {
-        const int l = wave, lp = q;
-        double acc = 0;
-        if (l < lp && lp < nb)
-            for (int64_t i = k0 + lp + lane; i < M; i += 64) acc = fma(V[l * M + i], V[lp * M + i], acc);
-        acc = wave_sum(acc);
-        if (lane == 0) S[l][lp] = acc;
-    }
-    __syncthreads();
-    if (threadIdx.x < QNB * QNB) Tf[threadIdx.x >> 4][threadIdx.x & 15] = 0.0;
-    __syncthreads();
-    for (int j = 0; j < nb; ++j) {
-        const double tj = tau[J.c_off + k0 + j];
-        if (threadIdx.x < j) {
-            const int i = threadIdx.x;
-            double acc = 0;
-            for (int m = i; m < j; ++m) acc = fma(Tf[i][m], S[m][j], acc);
-            Tf[i][j] = -tj * acc;
-        } else if (threadIdx.x == j)
-            Tf[j][j] = tj;
-        __syncthreads();
-    }
-    if (threadIdx.x < QNB * QNB)
-        Tfac[(J.pad0 + blockIdx.x) * (QNB * QNB) + threadIdx.x] = Tf[threadIdx.x >> 4][threadIdx.x & 15];
-}
-
-// C[k0:, tile] <- (I - V Tf V^T) C[k0:, tile]   for one block of 16 reflectors and a 16-column tile of C (M x r)
-__global__ __launch_bounds__(NTR) void qrp_apply_q_block_kernel(const QrpJob *__restrict__ jobs,
-                                                                const QrpState *__restrict__ state, int blk,
-                                                                double *__restrict__ C, const double *__restrict__ Vall,
-                                                                const double *__restrict__ Tfac) {
-    __shared__ WySmem<QNB> sm;
-    const int b = blockIdx.y;
-    const QrpJob J = jobs[b];
-    const int64_t r = state[b].rank;
-    const int64_t k0 = (int64_t)blk * QNB;
-    if (k0 >= r) return;
-    const int64_t j0 = (int64_t)blockIdx.x * RCOLS;
-    if (j0 >= r) return;
-    const int nb = (int)((r - k0 < QNB) ? (r - k0) : QNB);
-    if (threadIdx.x < QNB * QNB) sm.T[threadIdx.x >> 4][threadIdx.x & 15] = Tfac[(J.pad0 + blk) * (QNB * QNB) + threadIdx.x];
-    wy_apply_tile<QNB, false, false>(C + J.x_off, r, 1, k0, J.M, j0, r, Vall + J.x_off + k0 * J.M, nb, 0, sm);
-}
-
-// final outputs from T = Q_r U_R (M x r), S_R, VH_R (r x N) and the column permutation
-__global__ __launch_bounds__(NT) void qrp_output_kernel(const QrpJob *__restrict__ jobs, const SvdJob *__restrict__ sj,
-                                                        const QrpState *__restrict__ state, const double *__restrict__ T,
-                                                        const double *__restrict__ SR, const double *__restrict__ VHR,
-                                                        const int64_t *__restrict__ cperm, double *__restrict__ U,
-                                                        double *__restrict__ S, double *__restrict__ VH) {
-    const QrpJob J = jobs[blockIdx.y];
-    const SvdJob O = sj[blockIdx.y];
-    const int64_t r = state[blockIdx.y].rank, M = J.M, N = J.N, K = N;  // K = min(m, n)
-    const int64_t stride = (int64_t)gridDim.x * NT, t0 = (int64_t)blockIdx.x * NT + threadIdx.x;
-    for (int64_t e = t0; e < K; e += stride) S[O.s_off + e] = (e < r) ? SR[J.c_off + e] : 0.0;
-    if (!J.tr) {
-        // A = X (m = M >= n = N):  U = T (M x K, zero padded),  VH[jj][cperm[c]] = VH_R[jj][c]
-        for (int64_t e = t0; e < M * K; e += stride) {
-            const int64_t i = e / K, jj = e - i * K;
-            U[O.u_off + e] = (jj < r) ? T[J.x_off + i * r + jj] : 0.0;
-        }
-        for (int64_t e = t0; e < K * N; e += stride) {
-            const int64_t jj = e / N, c = e - jj * N;
-            VH[O.vh_off + jj * N + cperm[J.c_off + c]] = (jj < r) ? VHR[J.r_off + jj * N + c] : 0.0;
-        }
-    } else {
-        // A = X^T (m = N < n = M):  U[cperm[c]][jj] = VH_R[jj][c],  VH[jj][c] = T[c][jj]
-        for (int64_t e = t0; e < N * K; e += stride) {
-            const int64_t c = e / K, jj = e - c * K;
-            U[O.u_off + cperm[J.c_off + c] * K + jj] = (jj < r) ? VHR[J.r_off + jj * N + c] : 0.0;
-        }
-        for (int64_t e = t0; e < K * M; e += stride) {
-            const int64_t jj = e / M, c = e - jj * M;
-            VH[O.vh_off + e] = (jj < r) ? T[J.x_off + c * r + jj] : 0.0;
-        }
-    }
-}
-
-// ===================================================================================================
-// Complex version of the rank-revealing preconditioner (same structure; interleaved double2 storage).
-//   X = A (m >= n) or A^H (m < n), column-major;   X P = Q [R; 0],   H = I - tau v v^H (LAPACK zlarfg: beta real),
-//   the factorisation applies H^H from the left, blocks H_0 .. H_{l-1} = I - V T V^H (zlarft, forward / columnwise).
-//   A = X:    U = Q_r U_R,          VH[jj][cperm[c]] = VH_R[jj][c]
-//   A = X^H:  U[cperm[c]][jj] = conj(VH_R[jj][c]),   VH[jj][c] = conj((Q_r U_R)[c][jj])
-// Complex products on the matrix cores are 4 real MFMAs on the (re, im) planes of the fragments.
-typedef double2 cd;
-__device__ __forceinline__ cd c_mul(cd a, cd b) { return cd{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ cd c_mulc(cd a, cd b) { return cd{a.x * b.x + a.y * b.y, a.x * b.y - a.y * b.x}; }   // conj(a) * b
-__device__ __forceinline__ cd c_fma(cd a, cd b, cd acc) { return cd{acc.x + a.x * b.x - a.y * b.y, acc.y + a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ cd c_fmac(cd a, cd b, cd acc) { return cd{acc.x + a.x * b.x + a.y * b.y, acc.y + a.x * b.y - a.y * b.x}; }  // acc + conj(a) b
-
-__global__ __launch_bounds__(NT) void qrp_init_kernel_c(const QrpJob *__restrict__ jobs, const SvdJob *__restrict__ sj,
-                                                        const cd *__restrict__ A, cd *__restrict__ X,
-                                                        double *__restrict__ cn, int64_t *__restrict__ cperm,
-                                                        QrpState *__restrict__ state) {
-    // grid (column tiles of 64, jobs); wave w owns the columns j0 + 16 w .. +15, lanes run along the rows
-    __shared__ double tr_[64][65], ti_[64][65];
-    const QrpJob J = jobs[blockIdx.y];
-    const SvdJob S = sj[blockIdx.y];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t j0 = (int64_t)blockIdx.x * 64;
-    if (j0 >= J.N) return;
-    double acc[16];
-#pragma unroll
-    for (int rr = 0; rr < 16; ++rr) acc[rr] = 0.0;
-    for (int64_t i0 = 0; i0 < J.M; i0 += 64) {
-        if (!J.tr) {
-            __syncthreads();
-#pragma unroll
-            for (int rr = 0; rr < 16; ++rr) {
-                const int64_t i = i0 + wave * 16 + rr, j = j0 + lane;
-                const cd v = (i < J.M && j < J.N) ? A[S.a_off + i * S.n + j] : cd{0.0, 0.0};
-                tr_[wave * 16 + rr][lane] = v.x;
-                ti_[wave * 16 + rr][lane] = v.y;
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int rr = 0; rr < 16; ++rr) {
-            const int64_t j = j0 + wave * 16 + rr, i = i0 + lane;
-            if (j < J.N && i < J.M) {
-                cd v;
-                if (J.tr) {          // X = A^H:  X[i][j] = conj(A[j][i])
-                    v = A[S.a_off + j * S.n + i];
-                    v.y = -v.y;
-                } else
-                    v = cd{tr_[lane][wave * 16 + rr], ti_[lane][wave * 16 + rr]};
-                X[J.x_off + j * J.M + i] = v;
-                acc[rr] = fma(v.x, v.x, fma(v.y, v.y, acc[rr]));
-            }
-        }
-    }
-#pragma unroll
-    for (int rr = 0; rr < 16; ++rr) {
-        const double t = wave_sum(acc[rr]);
-        const int64_t j = j0 + wave * 16 + rr;
-        if (lane == 0 && j < J.N) {
-            cn[J.c_off + j] = t;
-            cperm[J.c_off + j] = j;
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) state[blockIdx.y] = QrpState{0, 0, 0, 0};
-}
-
-constexpr int KC = 2 * PNB + 1;   // real values reduced together in the complex panel kernel
-
-template <int NTP, int K>
-__device__ __forceinline__ void block_sum_arr(double (&v)[K], double (*red)[KC]) {
-#pragma unroll
-    for (int q = 0; q < K; ++q) v[q] = wave_sum(v[q]);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int q = 0; q < K; ++q) red[threadIdx.x >> 6][q] = v[q];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < K; ++q) {
-        double t = 0;
-#pragma unroll
-        for (int w = 0; w < NTP / 64; ++w) t += red[w][q];
-        v[q] = t;
-    }
-}
-
-template <int NTP, int RPT>
-__global__ __launch_bounds__(NTP) void qrp_panel_kernel_c(const QrpJob *__restrict__ jobs, int k, cd *__restrict__ X,
-                                                          cd *__restrict__ Vall, double *__restrict__ cn,
-                                                          cd *__restrict__ tau, int64_t *__restrict__ cperm,
-                                                          QrpState *__restrict__ state, const double *__restrict__ fro2,
-                                                          double tol2, cd *__restrict__ Tpan, int pivot) {
-    __shared__ double rv[NTP / 64];
-    __shared__ int64_t ri[NTP / 64];
-    __shared__ double red[NTP / 64][KC];
-    __shared__ int64_t s_p[PNB];
-    __shared__ int s_nbk;
-    __shared__ cd s_alpha, s_vrow[PNB], Tf[PNB][PNB];
-    const int b = blockIdx.x;
-    const QrpJob J = jobs[b];
-    const QrpState st0 = state[b];
-    if (st0.done) return;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t M = J.M, N = J.N;
-    const int64_t Kmax = (M < N) ? M : N;      // number of reflectors (N <= M in the pivoted use)
-    if (st0.last || k >= Kmax) {
-        if (tid == 0) state[b] = QrpState{st0.last ? st0.rank : (int)Kmax, 1, 0, 0};
-        return;
-    }
-    double cand[RPT];
-#pragma unroll
-    for (int t = 0; t < RPT; ++t) {
-        const int64_t j = tid + (int64_t)t * NTP;
-        cand[t] = (j < N) ? cn[J.c_off + j] : -4.0;
-    }
-    const double thresh = tol2 * fro2[b];
-    if (tid == 0) s_nbk = 0;
-    if (!pivot) {   // plain QR: the next PNB columns in their natural order, no rank test
-        if (tid == 0) {
-            const int nb_ = (int)((Kmax - k < PNB) ? (Kmax - k) : PNB);
-            for (int l = 0; l < nb_; ++l) s_p[l] = (int64_t)k + l;
-            s_nbk = nb_;
-        }
-        __syncthreads();
-    } else
-    for (int l = 0; l < PNB; ++l) {
-        double bv = -3.0;
-        int64_t bidx = N;
-#pragma unroll
-        for (int t = 0; t < RPT; ++t)
-            if (cand[t] > bv) {
-                bv = cand[t];
-                bidx = tid + (int64_t)t * NTP;
-            }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ov = __shfl_xor(bv, off, 64);
-            const int64_t oi = __shfl_xor(bidx, off, 64);
-            if (ov > bv || (ov == bv && oi < bidx)) {
-                bv = ov;
-                bidx = oi;
-            }
-        }
-        __syncthreads();
-        if (lane == 0) {
-            rv[wave] = bv;
-            ri[wave] = bidx;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double v0 = rv[0];
-            int64_t i0 = ri[0];
-            for (int w = 1; w < NTP / 64; ++w)
-                if (rv[w] > v0 || (rv[w] == v0 && ri[w] < i0)) {
-                    v0 = rv[w];
-                    i0 = ri[w];
-                }
-            if (v0 > thresh && s_nbk == l) {
-                s_p[l] = i0;
-                s_nbk = l + 1;
-            }
-        }
-        __syncthreads();
-        if (s_nbk <= l) break;
-        const int64_t w = s_p[l];
-#pragma unroll
-        for (int t = 0; t < RPT; ++t)
-            if (tid + (int64_t)t * NTP == w) cand[t] = -4.0;
-    }
-    const int nbk = s_nbk;
-    if (nbk == 0) {
-        if (tid == 0) state[b] = QrpState{k, 1, 0, 0};
-        return;
-    }
-    if (tid == 0) {
-        const bool last = (nbk < PNB);
-        state[b] = QrpState{last ? k + nbk : 0, 0, nbk, last ? 1 : 0};
-        for (int x = 0; x < PNB; ++x)
-            for (int y = 0; y < PNB; ++y) Tf[x][y] = cd{0.0, 0.0};
-    }
-    if (tid < nbk) {
-        cperm[J.c_off + k + tid] = s_p[tid];
-        cn[J.c_off + s_p[tid]] = -1.0;
-    }
-    __syncthreads();
-    cd *Xb = X + J.x_off;
-    cd c[PNB][RPT];
-#pragma unroll
-    for (int t = 0; t < RPT; ++t) {
-        const int64_t i = tid + (int64_t)t * NTP;
-#pragma unroll
-        for (int l = 0; l < PNB; ++l) c[l][t] = (i < M && l < nbk) ? Xb[s_p[l] * M + i] : cd{0.0, 0.0};
-    }
-#pragma clang loop unroll(full)
-    for (int l = 0; l < PNB; ++l) {
-        if (l < nbk) {
-            const int64_t kl = (int64_t)k + l;
-            if (l > 0) {
-                // c_l <- (I - V T^H V^H) c_l :  y = V^H c_l,  z = T^H y,  c_l -= V z
-                double y[2 * PNB];
-#pragma unroll
-                for (int m = 0; m < PNB; ++m) {
-                    cd a{0.0, 0.0};
-                    if (m < l) {
-#pragma unroll
-                        for (int t = 0; t < RPT; ++t) a = c_fmac(c[m][t], c[l][t], a);
-                    }
-                    y[2 * m] = a.x;
-                    y[2 * m + 1] = a.y;
-                }
-                block_sum_arr<NTP, 2 * PNB>(y, red);
-                cd z[PNB];
-#pragma unroll
-                for (int m = 0; m < PNB; ++m) {
-                    z[m] = cd{0.0, 0.0};
-                    if (m < l) {
-#pragma unroll
-                        for (int mm = 0; mm < PNB; ++mm)
-                            if (mm <= m) z[m] = c_fmac(Tf[mm][m], cd{y[2 * mm], y[2 * mm + 1]}, z[m]);
-                    }
-                }
-#pragma unroll
-                for (int m = 0; m < PNB; ++m)
-                    if (m < l) {
-                        const cd zn{-z[m].x, -z[m].y};
-#pragma unroll
-                        for (int t = 0; t < RPT; ++t) c[l][t] = c_fma(c[m][t], zn, c[l][t]);
-                    }
-            }
-            double g[KC];
-#pragma unroll
-            for (int q = 0; q < KC; ++q) g[q] = 0.0;
-#pragma unroll
-            for (int t = 0; t < RPT; ++t) {
-                const int64_t i = tid + (int64_t)t * NTP;
-                if (i > kl && i < M) {
-                    g[2 * PNB] = fma(c[l][t].x, c[l][t].x, fma(c[l][t].y, c[l][t].y, g[2 * PNB]));
-#pragma unroll
-                    for (int m = 0; m < PNB; ++m)
-                        if (m < l) {
-                            const cd a = c_mulc(c[m][t], c[l][t]);
-                            g[2 * m] += a.x;
-                            g[2 * m + 1] += a.y;
-                        }
-                } else if (i == kl) {
-                    s_alpha = c[l][t];
-#pragma unroll
-                    for (int m = 0; m < PNB; ++m)
-                        if (m < l) s_vrow[m] = c[m][t];
-                }
-            }
-            block_sum_arr<NTP, KC>(g, red);
-            const double s2 = g[2 * PNB];
-            const cd alpha = s_alpha;
-            double beta = alpha.x;
-            cd tk{0.0, 0.0}, scale{0.0, 0.0};
-            if (s2 > 0.0 || alpha.y != 0.0) {       // zlarfg
-                beta = -copysign(sqrt(alpha.x * alpha.x + alpha.y * alpha.y + s2), alpha.x);
-                tk = cd{(beta - alpha.x) / beta, -alpha.y / beta};
-                const double dr = alpha.x - beta, di = alpha.y, dn = dr * dr + di * di;
-                scale = cd{dr / dn, -di / dn};      // 1 / (alpha - beta)
-            }
-            // column l of T:  T[i2][l] = -tau sum_{m=i2}^{l-1} T[i2][m] (v_m^H v_l),  v_m^H v_l = g_m scale + conj(v_m[kl])
-            if (tid < l) {
-                cd acc{0.0, 0.0};
-#pragma unroll
-                for (int m = 0; m < PNB; ++m)
-                    if (m >= tid && m < l) {
-                        cd sml = c_mul(cd{g[2 * m], g[2 * m + 1]}, scale);
-                        sml.x += s_vrow[m].x;
-                        sml.y -= s_vrow[m].y;
-                        acc = c_fma(Tf[tid][m], sml, acc);
-                    }
-                const cd r = c_mul(tk, acc);
-                Tf[tid][l] = cd{-r.x, -r.y};
-            } else if (tid == l) {
-                Tf[l][l] = tk;
-                tau[J.c_off + kl] = tk;
-            }
-            cd *vk = Vall + J.x_off + kl * M;
-            cd *xc = Xb + s_p[l] * M;
-#pragma unroll
-            for (int t = 0; t < RPT; ++t) {
-                const int64_t i = tid + (int64_t)t * NTP;
-                if (i < M) {
-                    cd v;
-                    if (i < kl) {
-                        v = cd{0.0, 0.0};
-                        xc[i] = c[l][t];
-                    } else if (i == kl) {
-                        xc[i] = cd{beta, 0.0};
-                        v = cd{1.0, 0.0};
-                    } else {
-                        xc[i] = cd{0.0, 0.0};
-                        v = c_mul(c[l][t], scale);
-                    }
-                    vk[i] = v;
-                    c[l][t] = v;
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (tid < PNB * PNB) Tpan[(int64_t)b * PNB * PNB + tid] = Tf[tid / PNB][tid % PNB];
-}
-
-template <int NB>
-struct WySmemC {
-    double redr[NTR / 64][NB][RCOLS], redi[NTR / 64][NB][RCOLS];
-    cd Y[NB][RCOLS], Z[NB][RCOLS], T[NB][NB];
-    double nrm[NTR / 64][RCOLS];
-};
-
-// complex compact-WY tile:  C[k0:, tile] <- (I - V T' V^H) C[k0:, tile],  T' = T^H (CONJT: factorisation) or T (forming Q U_R)
-template <int NB, bool CONJT, bool NORMS>
-__device__ __forceinline__ double wy_apply_tile_c(cd *Cb, int64_t rs, int64_t cs, int64_t k0, int64_t M, int64_t j0, int64_t jend,
-                                                  const cd *__restrict__ V, int nb, int64_t kend, WySmemC<NB> &sm,
-                                                  bool col_ok = true) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int lo = lane & 15, kq = lane >> 4;
-    const int64_t j = j0 + lo;
-    const bool jok = (j < jend) && col_ok;
-    // ---- pass 1: Y(l, j) = sum_i conj(V(l, i)) C(i, j)
-    d4 ar = {0, 0, 0, 0}, ai = {0, 0, 0, 0};
-    for (int64_t i0 = k0 + 16 * wave; i0 < M; i0 += 16 * (NTR / 64)) {
-        cd a[4], bb[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int64_t i = i0 + 4 * kq + q;
-            const bool iok = i < M;
-            a[q] = (iok && lo < nb) ? V[(int64_t)lo * M + i] : cd{0.0, 0.0};
-            bb[q] = (iok && jok) ? Cb[i * rs + j * cs] : cd{0.0, 0.0};
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            ar = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q].x, bb[q].x, ar, 0, 0, 0);
-            ar = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q].y, bb[q].y, ar, 0, 0, 0);
-            ai = __builtin_amdgcn_mfma_f64_16x16x4f64(a[q].x, bb[q].y, ai, 0, 0, 0);
-            ai = __builtin_amdgcn_mfma_f64_16x16x4f64(-a[q].y, bb[q].x, ai, 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg)
-        if (kq + 4 * reg < NB) {
-            sm.redr[wave][kq + 4 * reg][lo] = ar[reg];
-            sm.redi[wave][kq + 4 * reg][lo] = ai[reg];
-        }
-    __syncthreads();
-    if (threadIdx.x < NB * RCOLS) {
-        const int l = threadIdx.x >> 4, c = threadIdx.x & 15;
-        double tr = 0, ti = 0;
-#pragma unroll
-        for (int q = 0; q < NTR / 64; ++q) {
-            tr += sm.redr[q][l][c];
-            ti += sm.redi[q][l][c];
-        }
-        sm.Y[l][c] = cd{tr, ti};
-    }
-    __syncthreads();
-    if (threadIdx.x < NB * RCOLS) {
-        const int l = threadIdx.x >> 4, c = threadIdx.x & 15;
-        cd t{0.0, 0.0};
-#pragma unroll
-        for (int m = 0; m < NB; ++m) t = CONJT ? c_fmac(sm.T[m][l], sm.Y[m][c], t) : c_fma(sm.T[l][m], sm.Y[m][c], t);
-        sm.Z[l][c] = cd{-t.x, -t.y};
-    }
-    __syncthreads();
-    cd zneg[NB / 4];
-#pragma unroll
-    for (int q = 0; q < NB / 4; ++q) zneg[q] = sm.Z[4 * q + kq][lo];
-    // ---- pass 2: C += V Zneg
-    double nrm = 0;
-    for (int64_t i0 = k0 + 16 * wave; i0 < M; i0 += 2 * 16 * (NTR / 64)) {
-        d4 cr[2], ci[2];
-        cd av[2][NB / 4];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int64_t ib = i0 + (int64_t)h * 16 * (NTR / 64);
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int64_t i = ib + kq + 4 * reg;
-                const cd v = (i < M && jok) ? Cb[i * rs + j * cs] : cd{0.0, 0.0};
-                cr[h][reg] = v.x;
-                ci[h][reg] = v.y;
-            }
-#pragma unroll
-            for (int q = 0; q < NB / 4; ++q) {
-                const int64_t i = ib + lo;
-                const int l = 4 * q + kq;
-                av[h][q] = (i < M && l < nb) ? V[(int64_t)l * M + i] : cd{0.0, 0.0};
-            }
-        }
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int q = 0; q < NB / 4; ++q) {
-                cr[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[h][q].x, zneg[q].x, cr[h], 0, 0, 0);
-                cr[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(-av[h][q].y, zneg[q].y, cr[h], 0, 0, 0);
-                ci[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[h][q].x, zneg[q].y, ci[h], 0, 0, 0);
-                ci[h] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[h][q].y, zneg[q].x, ci[h], 0, 0, 0);
-            }
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int64_t ib = i0 + (int64_t)h * 16 * (NTR / 64);
-#pragma unroll
-            for (int reg = 0; reg < 4; ++reg) {
-                const int64_t i = ib + kq + 4 * reg;
-                if (i < M && jok) {
-                    Cb[i * rs + j * cs] = cd{cr[h][reg], ci[h][reg]};
-                    if (NORMS && i >= kend) nrm = fma(cr[h][reg], cr[h][reg], fma(ci[h][reg], ci[h][reg], nrm));
-                }
-            }
-        }
-    }
-    if (!NORMS) return 0.0;
-    nrm += __shfl_xor(nrm, 16, 64);
-    nrm += __shfl_xor(nrm, 32, 64);
-    if (lane < RCOLS) sm.nrm[wave][lo] = nrm;
-    __syncthreads();
-    double t = 0;
-    if (threadIdx.x < RCOLS) {
-#pragma unroll
-        for (int q = 0; q < NTR / 64; ++q) t += sm.nrm[q][threadIdx.x];
-    }
-    return t;
-}
-
-__global__ __launch_bounds__(NTR) void qrp_update_kernel_c(const QrpJob *__restrict__ jobs, int k, cd *__restrict__ X,
-                                                           const cd *__restrict__ Vall, double *__restrict__ cn,
-                                                           const QrpState *__restrict__ state, const cd *__restrict__ Tpan) {
-    __shared__ WySmemC<PNB> sm;
-    const int b = blockIdx.y;
-    const QrpState st = state[b];
-    if (st.done || st.nbk == 0) return;
-    const QrpJob J = jobs[b];
-    const int nbk = st.nbk;
-    const int64_t j0 = (int64_t)blockIdx.x * RCOLS;
-    if (j0 >= J.N) return;
-    const int64_t jl = j0 + (threadIdx.x & (RCOLS - 1));
-    const bool col_ok = (jl < J.N) && (cn[J.c_off + jl] >= 0.0);
-    if (__ballot(col_ok) == 0) return;
-    if (threadIdx.x < PNB * PNB) sm.T[threadIdx.x / PNB][threadIdx.x % PNB] = Tpan[(int64_t)b * PNB * PNB + threadIdx.x];
-    const double nrm = wy_apply_tile_c<PNB, true, true>(X + J.x_off, 1, J.M, k, J.M, j0, J.N, Vall + J.x_off + (int64_t)k * J.M,
-                                                        nbk, (int64_t)k + nbk, sm, col_ok);
-    if (threadIdx.x < RCOLS && col_ok) cn[J.c_off + jl] = nrm;
-}
-
-__global__ __launch_bounds__(NT) void qrp_extract_kernel_c(const QrpJob *__restrict__ jobs, const QrpState *__restrict__ state,
-                                                           const cd *__restrict__ X, const int64_t *__restrict__ cperm,
-                                                           cd *__restrict__ Rtop) {
-    const QrpJob J = jobs[blockIdx.y];
-    const int64_t r = state[blockIdx.y].rank, N = J.N;
-    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < r * N; e += (int64_t)gridDim.x * NT) {
-        const int64_t i = e / N, j = e - i * N;
-        Rtop[J.r_off + e] = (j >= i) ? X[J.x_off + cperm[J.c_off + j] * J.M + i] : cd{0.0, 0.0};
-    }
-}
-
-__global__ __launch_bounds__(NT) void qrp_form_t_kernel_c(const QrpJob *__restrict__ jobs, const QrpState *__restrict__ state,
-                                                          const cd *__restrict__ UR, cd *__restrict__ T) {
-    const QrpJob J = jobs[blockIdx.y];
-    const int64_t r = state[blockIdx.y].rank, M = J.M;
-    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < M * r; e += (int64_t)gridDim.x * NT) {
-        const int64_t i = e / r;
-        T[J.x_off + e] = (i < r) ? UR[J.r_off + e] : cd{0.0, 0.0};
-    }
-}
-
-__global__ __launch_bounds__(NTR) void qrp_tfactor_kernel_c(const QrpJob *__restrict__ jobs, const QrpState *__restrict__ state,
-                                                            const cd *__restrict__ Vall, const cd *__restrict__ tau,
-                                                            cd *__restrict__ Tfac) {
-    __shared__ cd S[QNB][QNB + 1];
-    __shared__ cd Tf[QNB][QNB + 1];
-    const QrpJob J = jobs[blockIdx.y];
-    const int64_t r = state[blockIdx.y].rank, M = J.M;
-    const int64_t k0 = (int64_t)blockIdx.x * QNB;
-    if (k0 >= r) return;
-    const int nb = (int)((r - k0 < QNB) ? (r - k0) : QNB);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const cd *V = Vall + J.x_off + k0 * M;
-    for (int q = 0; q < QNB; ++q) {          // S[l][l'] = v_l^H v_l'
-        const int l = wave, lp = q;
-        cd acc{0.0, 0.0};
-        if (l < lp && lp < nb)
-            for (int64_t i = k0 + lp + lane; i < M; i += 64) acc = c_fmac(V[l * M + i], V[lp * M + i], acc);
-        acc.x = wave_sum(acc.x);
-        acc.y = wave_sum(acc.y);
-        if (lane == 0) S[l][lp] = acc;
-    }
-    __syncthreads();
-    if (threadIdx.x < QNB * QNB) Tf[threadIdx.x >> 4][threadIdx.x & 15] = cd{0.0, 0.0};
-    __syncthreads();
-    for (int j = 0; j < nb; ++j) {
-        const cd tj = tau[J.c_off + k0 + j];
-        if (threadIdx.x < j) {
-            const int i = threadIdx.x;
-            cd acc{0.0, 0.0};
-            for (int m = i; m < j; ++m) acc = c_fma(Tf[i][m], S[m][j], acc);
-            const cd rr = c_mul(tj, acc);
-            Tf[i][j] = cd{-rr.x, -rr.y};
-        } else if (threadIdx.x == j)
-            Tf[j][j] = tj;
-        __syncthreads();
-    }
-    if (threadIdx.x < QNB * QNB)
-        Tfac[(J.pad0 + blockIdx.x) * (QNB * QNB) + threadIdx.x] = Tf[threadIdx.x >> 4][threadIdx.x & 15];
-}
-
-__global__ __launch_bounds__(NTR) void qrp_apply_q_block_kernel_c(const QrpJob *__restrict__ jobs,
-                                                                  const QrpState *__restrict__ state, int blk,
-                                                                  cd *__restrict__ C, const cd *__restrict__ Vall,
-                                                                  const cd *__restrict__ Tfac) {
-    __shared__ WySmemC<QNB> sm;
-    const int b = blockIdx.y;
-    const QrpJob J = jobs[b];
-    const int64_t r = state[b].rank;
-    const int64_t k0 = (int64_t)blk * QNB;
-    if (k0 >= r) return;
-    const int64_t j0 = (int64_t)blockIdx.x * RCOLS;
-    if (j0 >= r) return;
-    const int nb = (int)((r - k0 < QNB) ? (r - k0) : QNB);
-    if (threadIdx.x < QNB * QNB) sm.T[threadIdx.x >> 4][threadIdx.x & 15] = Tfac[(J.pad0 + blk) * (QNB * QNB) + threadIdx.x];
-    wy_apply_tile_c<QNB, false, false>(C + J.x_off, r, 1, k0, J.M, j0, r, Vall + J.x_off + k0 * J.M, nb, 0, sm);
-}
-
-__global__ __launch_bounds__(NT) void qrp_output_kernel_c(const QrpJob *__restrict__ jobs, const SvdJob *__restrict__ sj,
-                                                          const QrpState *__restrict__ state, const cd *__restrict__ T,
-                                                          const double *__restrict__ SR, const cd *__restrict__ VHR,
-                                                          const int64_t *__restrict__ cperm, cd *__restrict__ U,
-                                                          double *__restrict__ S, cd *__restrict__ VH) {
-    const QrpJob J = jobs[blockIdx.y];
-    const SvdJob O = sj[blockIdx.y];
-    const int64_t r = state[blockIdx.y].rank, M = J.M, N = J.N, K = N;
-    const int64_t stride = (int64_t)gridDim.x * NT, t0 = (int64_t)blockIdx.x * NT + threadIdx.x;
-    const cd zero{0.0, 0.0};
-    for (int64_t e = t0; e < K; e += stride) S[O.s_off + e] = (e < r) ? SR[J.c_off + e] : 0.0;
-    if (!J.tr) {
-        for (int64_t e = t0; e < M * K; e += stride) {
-            const int64_t i = e / K, jj = e - i * K;
-            U[O.u_off + e] = (jj < r) ? T[J.x_off + i * r + jj] : zero;
-        }
-        for (int64_t e = t0; e < K * N; e += stride) {
-            const int64_t jj = e / N, c = e - jj * N;
-            VH[O.vh_off + jj * N + cperm[J.c_off + c]] = (jj < r) ? VHR[J.r_off + jj * N + c] : zero;
-        }
-    } else {
-        for (int64_t e = t0; e < N * K; e += stride) {
-            const int64_t c = e / K, jj = e - c * K;
-            cd v = (jj < r) ? VHR[J.r_off + jj * N + c] : zero;
-            v.y = -v.y;
-            U[O.u_off + cperm[J.c_off + c] * K + jj] = v;
-        }
-        for (int64_t e = t0; e < K * M; e += stride) {
-            const int64_t jj = e / M, c = e - jj * M;
-            cd v = (jj < r) ? T[J.x_off + c * r + jj] : zero;
-            v.y = -v.y;
-            VH[O.vh_off + e] = v;
-        }
-    }
-}
+// Householder family (pivoted QR, compact-WY trailing update, blocked application of Q): one scalar-templated set of kernels
+// for f64 and c128
+#include "tpa_qrp.inc"
 
 int tpa_svd_use_qrp = 1;   // real data: rank-revealing pivoted QR before the Jacobi iteration
 
@@ -3719,11 +2568,12 @@ inline QrpPoll &qrp_poll() {
 template <bool CPLX>
 int svd_run_qrp(const Layout &lay, const QrpLayout &q, int n_jobs, const void *a_base, void *u_base, double *s_dev,
                 void *vh_base, char *work, int max_sweeps, int *sweeps_done, hipStream_t st, double rho) {
+    using T = std::conditional_t<CPLX, cd, double>;
     const int dtype = CPLX ? TPA_C128 : TPA_F64;
-    void *X = work + q.off_x, *Vall = work + q.off_vall;
-    void *Rtop = work + q.off_rtop, *UR = work + q.off_ur, *VHR = work + q.off_vhr;
+    T *X = (T *)(work + q.off_x), *Vall = (T *)(work + q.off_vall);
+    T *Rtop = (T *)(work + q.off_rtop), *UR = (T *)(work + q.off_ur), *VHR = (T *)(work + q.off_vhr);
     double *cn = (double *)(work + q.off_cn), *SR = (double *)(work + q.off_sr);
-    void *tau = work + q.off_tau;
+    T *tau = (T *)(work + q.off_tau), *Tpan = (T *)(work + q.off_tpan), *Tfac = (T *)(work + q.off_tfac);
     int64_t *cperm = (int64_t *)(work + q.off_cperm);
     QrpJob *qjobs = (QrpJob *)(work + q.off_qjobs);
     SvdJob *sjobs = (SvdJob *)(work + q.off_sjobs);
@@ -3741,37 +2591,16 @@ int svd_run_qrp(const Layout &lay, const QrpLayout &q, int n_jobs, const void *a
     svd_fro_sum_kernel<<<n_jobs, 64, 0, st>>>(sjobs, fpart, fro2);
     { const char *e = getenv("TPA_SVD_SMALL_PANEL"); if (e) tpa_svd_small_panel = atoi(e); }
     const int nmax = (int)q.n_max;
-    if (CPLX)
-        qrp_init_kernel_c<<<dim3((nmax + 63) / 64, n_jobs), NT, 0, st>>>(qjobs, sjobs, (const cd *)a_base, (cd *)X, cn, cperm, state);
-    else
-        qrp_init_kernel<<<dim3((nmax + 63) / 64, n_jobs), NT, 0, st>>>(qjobs, sjobs, (const double *)a_base, (double *)X, cn, cperm, state);
+    qrp_init_kernel<T><<<dim3((nmax + 63) / 64, n_jobs), NT, 0, st>>>(qjobs, sjobs, (const T *)a_base, X, cn, cperm, state);
     TPA_LAUNCH_CHECK();
     std::vector<QrpState> hstate(n_jobs);
     const double tol2 = QRP_RANK_TOL * QRP_RANK_TOL;
-    void *Tpan = work + q.off_tpan;
     bool finished = false;
     for (int k = 0, step = 0;; k += PNB, ++step) {
-        if (CPLX) {
-            if (q.m_max <= 4 * 256)
-                qrp_panel_kernel_c<256, 4><<<n_jobs, 256, 0, st>>>(qjobs, k, (cd *)X, (cd *)Vall, cn, (cd *)tau, cperm, state, fro2, tol2, (cd *)Tpan, 1);
-            else
-                qrp_panel_kernel_c<256, 8><<<n_jobs, 256, 0, st>>>(qjobs, k, (cd *)X, (cd *)Vall, cn, (cd *)tau, cperm, state, fro2, tol2, (cd *)Tpan, 1);
-        } else if (q.m_max <= 8 * 64 && q.n_max <= 8 * 64 && tpa_svd_small_panel)
-            // small blocks (chi <= 512, Hubbard ladders): the whole panel in ONE wavefront -- no workgroup barriers, no LDS stage in
-            // the reductions (for >= 1000 rows this variant was 1.6x slower, here the barriers are all there is to save)
-            qrp_panel_kernel<64, 8><<<n_jobs, 64, 0, st>>>(qjobs, k, (double *)X, (double *)Vall, cn, (double *)tau, cperm, state, fro2, tol2, (double *)Tpan, 1);
-        else if (q.m_max <= 8 * 256)
-            qrp_panel_kernel<256, 8><<<n_jobs, 256, 0, st>>>(qjobs, k, (double *)X, (double *)Vall, cn, (double *)tau, cperm, state, fro2, tol2, (double *)Tpan, 1);
-        else if (q.m_max <= 16 * 256)
-            qrp_panel_kernel<256, 16><<<n_jobs, 256, 0, st>>>(qjobs, k, (double *)X, (double *)Vall, cn, (double *)tau, cperm, state, fro2, tol2, (double *)Tpan, 1);
-        else
-            qrp_panel_kernel<256, 32><<<n_jobs, 256, 0, st>>>(qjobs, k, (double *)X, (double *)Vall, cn, (double *)tau, cperm, state, fro2, tol2, (double *)Tpan, 1);
+        launch_qrp_panel<CPLX>(q.m_max, q.n_max, n_jobs, st, qjobs, k, X, Vall, cn, tau, cperm, state, fro2, Tpan, tol2, 1);
         if (k >= nmax) break;   // that launch only finalised the states
         const int tiles = (nmax + RCOLS - 1) / RCOLS;   // physical columns; finished ones are skipped inside
-        if (CPLX)
-            qrp_update_kernel_c<<<dim3(tiles, n_jobs), NTR, 0, st>>>(qjobs, k, (cd *)X, (const cd *)Vall, cn, state, (const cd *)Tpan);
-        else
-            qrp_update_kernel<<<dim3(tiles, n_jobs), NTR, 0, st>>>(qjobs, k, (double *)X, (const double *)Vall, cn, state, (const double *)Tpan);
+        qrp_update_kernel<T><<<dim3(tiles, n_jobs), NTR, 0, st>>>(qjobs, k, X, Vall, cn, state, Tpan);
         // "all blocks finished?" without draining the queue: every QRP_POLL steps the states are copied to pinned memory behind
         // the launches and the host only LOOKS at a copy once its event has fired, while it keeps enqueueing steps.  Steps that
         // turn out to be superfluous return at their first instruction (state.done).  (Round 3: the blocking poll left the GPU
@@ -3811,10 +2640,7 @@ int svd_run_qrp(const Layout &lay, const QrpLayout &q, int n_jobs, const void *a
     qrp_poll().drain();
     TPA_LAUNCH_CHECK();
     qrp_finish_perm_kernel<<<n_jobs, NT, 0, st>>>(qjobs, state, cn, cperm);
-    if (CPLX)
-        qrp_extract_kernel_c<<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, state, (const cd *)X, cperm, (cd *)Rtop);
-    else
-        qrp_extract_kernel<<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, state, (const double *)X, cperm, (double *)Rtop);
+    qrp_extract_kernel<T><<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, state, X, cperm, Rtop);
     {   // final states and ||A||_F^2 (NaN / Inf in the input: not finite -- the pivot search would silently report rank 0): one wait
         QrpState *pst = (QrpState *)pin_stage().take((size_t)n_jobs * sizeof(QrpState), st);
         double *hfro = (double *)pin_stage().take((size_t)n_jobs * 8, st);
@@ -3857,24 +2683,13 @@ int svd_run_qrp(const Layout &lay, const QrpLayout &q, int n_jobs, const void *a
         }
         rc = svd_run<CPLX>(nlay, nn, Rtop, UR, SR, VHR, work + q.off_nested, max_sweeps, sweeps_done, st, rho);
         if (rc != 0 && rc != TPA_E_NOCONV) return rc;
-        void *Tfac = work + q.off_tfac;
         const int nblk = (rmax + QNB - 1) / QNB;
-        if (CPLX) {
-            qrp_form_t_kernel_c<<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, state, (const cd *)UR, (cd *)X);
-            qrp_tfactor_kernel_c<<<dim3(nblk, n_jobs), NTR, 0, st>>>(qjobs, state, (const cd *)Vall, (const cd *)tau, (cd *)Tfac);
-            for (int blk = nblk - 1; blk >= 0; --blk)
-                qrp_apply_q_block_kernel_c<<<dim3((rmax + RCOLS - 1) / RCOLS, n_jobs), NTR, 0, st>>>(qjobs, state, blk, (cd *)X, (const cd *)Vall, (const cd *)Tfac);
-        } else {
-            qrp_form_t_kernel<<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, state, (const double *)UR, (double *)X);
-            qrp_tfactor_kernel<<<dim3(nblk, n_jobs), NTR, 0, st>>>(qjobs, state, (const double *)Vall, (const double *)tau, (double *)Tfac);
-            for (int blk = nblk - 1; blk >= 0; --blk)
-                qrp_apply_q_block_kernel<<<dim3((rmax + RCOLS - 1) / RCOLS, n_jobs), NTR, 0, st>>>(qjobs, state, blk, (double *)X, (const double *)Vall, (const double *)Tfac);
-        }
+        qrp_form_t_kernel<T><<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, state, UR, X);
+        qrp_tfactor_kernel<T><<<dim3(nblk, n_jobs), NTR, 0, st>>>(qjobs, state, Vall, tau, Tfac);
+        for (int blk = nblk - 1; blk >= 0; --blk)
+            qrp_apply_q_block_kernel<T><<<dim3((rmax + RCOLS - 1) / RCOLS, n_jobs), NTR, 0, st>>>(qjobs, state, blk, X, Vall, Tfac);
     }
-    if (CPLX)
-        qrp_output_kernel_c<<<dim3(128, n_jobs), NT, 0, st>>>(qjobs, sjobs, state, (const cd *)X, SR, (const cd *)VHR, cperm, (cd *)u_base, s_dev, (cd *)vh_base);
-    else
-        qrp_output_kernel<<<dim3(128, n_jobs), NT, 0, st>>>(qjobs, sjobs, state, (const double *)X, SR, (const double *)VHR, cperm, (double *)u_base, s_dev, (double *)vh_base);
+    qrp_output_kernel<T><<<dim3(128, n_jobs), NT, 0, st>>>(qjobs, sjobs, state, X, SR, VHR, cperm, (T *)u_base, s_dev, (T *)vh_base);
     TPA_LAUNCH_CHECK();
     TPA_HIP_CHECK(hipStreamSynchronize(st));
     return rc;
@@ -3915,7 +2730,8 @@ __global__ __launch_bounds__(NT) void qr_copy_q_kernel(const QrpJob *__restrict_
 
 template <bool CPLX>
 int qr_run_wy(const int64_t *jobs_host, int n_jobs, const void *a_base, void *q_base, void *r_base, hipStream_t st) {
-    const int64_t esz = CPLX ? 16 : 8;
+    using T = std::conditional_t<CPLX, cd, double>;
+    const int64_t esz = sizeof(T);
     std::vector<QrpJob> qj(n_jobs);
     std::vector<SvdJob> sj(n_jobs);
     std::vector<int64_t> qoffs(n_jobs);
@@ -3958,7 +2774,8 @@ int qr_run_wy(const int64_t *jobs_host, int n_jobs, const void *a_base, void *q_
                   off_tpan = take(2 * (int64_t)n_jobs * PNB * PNB * esz);      // (two slots: the look-ahead path ping-pongs)
     char *work = nullptr;
     TPA_HIP_CHECK(hipMallocAsync((void **)&work, (size_t)o, st));
-    void *X = work + off_x, *Vall = work + off_v, *tau = work + off_tau, *Tfac = work + off_tfac, *Tpan = work + off_tpan;
+    T *X = (T *)(work + off_x), *Vall = (T *)(work + off_v), *tau = (T *)(work + off_tau), *Tfac = (T *)(work + off_tfac),
+      *Tpan = (T *)(work + off_tpan);
     double *cn = (double *)(work + off_cn), *fro2 = (double *)(work + off_fro);
     int64_t *cperm = (int64_t *)(work + off_cperm), *qo_dev = (int64_t *)(work + off_qo);
     QrpJob *qjobs = (QrpJob *)(work + off_qj);
@@ -3976,10 +2793,7 @@ int qr_run_wy(const int64_t *jobs_host, int n_jobs, const void *a_base, void *q_
     if (!rc && (e = hipMemsetAsync(fro2, 0, n_jobs * 8, st)) != hipSuccess) fail(e);
     if (!rc) {
         const dim3 gcol((unsigned)((nmax + 63) / 64), n_jobs);
-        if (CPLX)
-            qrp_init_kernel_c<<<gcol, NT, 0, st>>>(qjobs, sjobs, (const cd *)a_base, (cd *)X, cn, cperm, state);
-        else
-            qrp_init_kernel<<<gcol, NT, 0, st>>>(qjobs, sjobs, (const double *)a_base, (double *)X, cn, cperm, state);
+        qrp_init_kernel<T><<<gcol, NT, 0, st>>>(qjobs, sjobs, (const T *)a_base, X, cn, cperm, state);
         const int tiles = (int)((nmax + RCOLS - 1) / RCOLS);
         bool tall = true;      // (wide blocks have columns beyond the last panel that belong to neither role of the fused step)
         for (int b = 0; b < n_jobs; ++b) tall = tall && (qj[b].M >= qj[b].N);
@@ -3997,40 +2811,18 @@ int qr_run_wy(const int64_t *jobs_host, int n_jobs, const void *a_base, void *q_
                                                             cperm, state, fro2, 0.0, (double *)Tpan, 0);
         }
         for (int k = 0; !lookahead; k += PNB) {
-            if (CPLX) {
-                if (mmax <= 4 * 256)
-                    qrp_panel_kernel_c<256, 4><<<n_jobs, 256, 0, st>>>(qjobs, k, (cd *)X, (cd *)Vall, cn, (cd *)tau, cperm, state, fro2, 0.0, (cd *)Tpan, 0);
-                else
-                    qrp_panel_kernel_c<256, 8><<<n_jobs, 256, 0, st>>>(qjobs, k, (cd *)X, (cd *)Vall, cn, (cd *)tau, cperm, state, fro2, 0.0, (cd *)Tpan, 0);
-            } else if (mmax <= 8 * 256)
-                qrp_panel_kernel<256, 8><<<n_jobs, 256, 0, st>>>(qjobs, k, (double *)X, (double *)Vall, cn, (double *)tau, cperm, state, fro2, 0.0, (double *)Tpan, 0);
-            else if (mmax <= 16 * 256)
-                qrp_panel_kernel<256, 16><<<n_jobs, 256, 0, st>>>(qjobs, k, (double *)X, (double *)Vall, cn, (double *)tau, cperm, state, fro2, 0.0, (double *)Tpan, 0);
-            else
-                qrp_panel_kernel<256, 32><<<n_jobs, 256, 0, st>>>(qjobs, k, (double *)X, (double *)Vall, cn, (double *)tau, cperm, state, fro2, 0.0, (double *)Tpan, 0);
+            launch_qrp_panel<CPLX>(mmax, nmax, n_jobs, st, qjobs, k, X, Vall, cn, tau, cperm, state, fro2, Tpan, 0.0, 0);
             if (k >= kmax) break;   // that launch only finalised the states (rank = min(m, n))
-            if (CPLX)
-                qrp_update_kernel_c<<<dim3(tiles, n_jobs), NTR, 0, st>>>(qjobs, k, (cd *)X, (const cd *)Vall, cn, state, (const cd *)Tpan);
-            else
-                qrp_update_kernel<<<dim3(tiles, n_jobs), NTR, 0, st>>>(qjobs, k, (double *)X, (const double *)Vall, cn, state, (const double *)Tpan);
+            qrp_update_kernel<T><<<dim3(tiles, n_jobs), NTR, 0, st>>>(qjobs, k, X, Vall, cn, state, Tpan);
         }
         const int nblk = (int)((kmax + QNB - 1) / QNB);
         const dim3 gq((unsigned)((kmax + RCOLS - 1) / RCOLS), n_jobs);
-        if (CPLX) {
-            qrp_extract_kernel_c<<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, state, (const cd *)X, cperm, (cd *)r_base);
-            qr_identity_kernel<true><<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, (double *)X);
-            qrp_tfactor_kernel_c<<<dim3(nblk, n_jobs), NTR, 0, st>>>(qjobs, state, (const cd *)Vall, (const cd *)tau, (cd *)Tfac);
-            for (int blk = nblk - 1; blk >= 0; --blk)
-                qrp_apply_q_block_kernel_c<<<gq, NTR, 0, st>>>(qjobs, state, blk, (cd *)X, (const cd *)Vall, (const cd *)Tfac);
-            qr_copy_q_kernel<true><<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, qo_dev, (const double *)X, (double *)q_base);
-        } else {
-            qrp_extract_kernel<<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, state, (const double *)X, cperm, (double *)r_base);
-            qr_identity_kernel<false><<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, (double *)X);
-            qrp_tfactor_kernel<<<dim3(nblk, n_jobs), NTR, 0, st>>>(qjobs, state, (const double *)Vall, (const double *)tau, (double *)Tfac);
-            for (int blk = nblk - 1; blk >= 0; --blk)
-                qrp_apply_q_block_kernel<<<gq, NTR, 0, st>>>(qjobs, state, blk, (double *)X, (const double *)Vall, (const double *)Tfac);
-            qr_copy_q_kernel<false><<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, qo_dev, (const double *)X, (double *)q_base);
-        }
+        qrp_extract_kernel<T><<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, state, X, cperm, (T *)r_base);
+        qr_identity_kernel<CPLX><<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, (double *)X);
+        qrp_tfactor_kernel<T><<<dim3(nblk, n_jobs), NTR, 0, st>>>(qjobs, state, Vall, tau, Tfac);
+        for (int blk = nblk - 1; blk >= 0; --blk)
+            qrp_apply_q_block_kernel<T><<<gq, NTR, 0, st>>>(qjobs, state, blk, X, Vall, Tfac);
+        qr_copy_q_kernel<CPLX><<<dim3(64, n_jobs), NT, 0, st>>>(qjobs, qo_dev, (const double *)X, (double *)q_base);
         if ((e = hipGetLastError()) != hipSuccess) fail(e);
     }
     (void)hipFreeAsync(work, st);

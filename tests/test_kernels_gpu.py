@@ -446,6 +446,83 @@ def test_qr_lookahead(env):
             assert (r0 - r2).abs().max().item() < 1e-12 * max(m, n) * mats[b].abs().max().item(), b
 
 
+def _qr_call(torch, lib, _lib, x, mode=0):
+    """tpa_qr_batch on one host matrix -> (q, r) host tensors."""
+    m, n = x.shape
+    k = min(m, n)
+    jh = np.array([[0, m, n, 0, 0, 0, 0, 0]], np.int64)
+    A = x.reshape(-1).cuda()
+    Q = torch.zeros(m * k, dtype=x.dtype).cuda()
+    R = torch.zeros(k * n, dtype=x.dtype).cuda()
+    lib.tpa_qr_set_algorithm(mode)
+    try:
+        _lib.check(lib.tpa_qr_batch(int(x.is_complex()), jh.ctypes.data, 1, A.data_ptr(), Q.data_ptr(), R.data_ptr(),
+                                    torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+    finally:
+        lib.tpa_qr_set_algorithm(0)
+    return Q.cpu().reshape(m, k), R.cpu().reshape(k, n)
+
+
+@pytest.mark.parametrize("cplx,m,n", [(False, 600, 40), (False, 2100, 40), (False, 4200, 40), (True, 600, 40), (True, 1100, 40)])
+def test_qr_wy_panel_variants(env, cplx, m, n):
+    """The panel kernel of the blocked QR is chosen per call from the tallest block: one call per variant.  f64 600 rows: one
+    launch per panel (tpa_qr_la.inc) and the closing <256, 8> state launch; 2100: <256, 16>; 4200: <256, 32>; c128 600: <256, 4>;
+    1100: <256, 8>.  Same assertions as test_qr_batch."""
+    torch, lib, _lib = env
+    g = torch.Generator(device="cpu").manual_seed(21)
+    dt = torch.complex128 if cplx else torch.float64
+    x = torch.randn(m, n, dtype=dt, generator=g)
+    dup = 37
+    x[:, dup] = x[:, dup - 1]      # linearly dependent columns
+    q, r = _qr_call(torch, lib, _lib, x)
+    assert (q @ r - x).abs().max().item() < 1e-12 * max(m, n)
+    assert (q.conj().T @ q - torch.eye(n, dtype=dt)).abs().max().item() < 1e-13 * max(m, n)
+    assert torch.tril(r, -1).abs().max().item() == 0.0
+    if cplx:
+        assert r.diagonal().imag.abs().max().item() == 0.0
+    if not cplx and m == 600:
+        # the two-launches-per-panel path (<256, 8>) does the same arithmetic per column; from the duplicated column on, rows
+        # >= dup of R are rounding noise in both
+        r2 = _qr_call(torch, lib, _lib, x, mode=2)[1]
+        d = (r - r2).abs()
+        d[dup:, dup:] = 0
+        assert d.max().item() < 1e-12 * max(m, n)
+
+
+@pytest.mark.parametrize("cplx,m,n,rank", [(False, 600, 48, 24), (False, 2100, 48, 24), (False, 48, 4200, 24),
+                                           (True, 1100, 48, 24), (True, 48, 1100, 24)])
+def test_svd_rank_revealing_panel_variants(env, cplx, m, n, rank):
+    """The panel kernel of the pivoted-QR preconditioner is chosen per call from the largest block: one call per variant that
+    test_svd_rank_revealing_path does not reach.  f64 600 rows: <256, 8> with pivoting; 2100: <256, 16>; 48 x 4200: <256, 32> on
+    X = A^T; c128 1100 rows: <256, 8>, as A and as A^H.  Same matrices and assertions as that test."""
+    torch, lib, _lib = env
+    g = torch.Generator(device="cpu").manual_seed(23)
+    dt = torch.complex128 if cplx else torch.float64
+    u0, _ = torch.linalg.qr(torch.randn(m, rank, dtype=dt, generator=g))
+    v0, _ = torch.linalg.qr(torch.randn(n, rank, dtype=dt, generator=g))
+    x = (u0 * torch.logspace(0, -9, rank, dtype=torch.float64).to(dt)) @ v0.conj().T
+    log = (ctypes.c_int64 * 8)()
+    lib.tpa_svd_call_log(log, 1, 1)
+    res, rc, _ = _svd_call(torch, lib, [x])
+    assert rc == 0
+    assert lib.tpa_svd_call_log(log, 1, 0) == 1 and log[4] == 1, "the call must take the pivoted-QR path"
+    u, s, vh = res[0]
+    ref = torch.linalg.svdvals(x)
+    scale = ref[0].item()
+    assert (s - ref).abs().max().item() <= 1e-13 * scale * max(m, n)
+    assert bool((s[:-1] >= s[1:]).all())
+    assert ((u * s.to(dt)) @ vh - x).abs().max().item() <= 1e-12 * scale * max(m, n)
+    nz = s > 1e-6 * scale
+    k = int(nz.sum())
+    assert k > 0
+    assert (u[:, nz].conj().T @ u[:, nz] - torch.eye(k, dtype=dt)).abs().max().item() < 1e-12
+    assert (vh[nz] @ vh[nz].conj().T - torch.eye(k, dtype=dt)).abs().max().item() < 1e-12
+    dead = s == 0      # beyond the numerical rank: exact zeros, zero vectors
+    if bool(dead.any()):
+        assert u[:, dead].abs().max().item() == 0.0
+
+
 @pytest.mark.parametrize("cplx", [False, True])
 def test_eigh_batch(env, cplx):
     torch, lib, _lib = env
