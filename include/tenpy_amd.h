@@ -288,7 +288,17 @@ int tpa_svd_set_rank_cap(int cap);
  *   Q_b m x k row-major, R_b k x n row-major, k = min(m,n).  A not overwritten.
  *   a_off is a signed element offset from a_base: the blocks of SEVERAL arenas may be factorised in one call by taking the
  *   lowest arena address as a_base (np_conserved.qr_batched: the bonds of one half-step of the QR-based TEBD, reference
- *   algorithms/tebd.py:374-414 / truncation.py:611-640). */
+ *   algorithms/tebd.py:374-414 / truncation.py:611-640).
+ * Pinned by tests/test_conformance_qr.py on every dispatch path:
+ *   - Q_b and R_b are written COMPLETELY, the zeros below the diagonal of R_b (+0.0) included: q_base / r_base may be
+ *     uninitialised memory (every caller passes such).  Nothing outside of the Q_b / R_b of the jobs is written, a_base is only read.
+ *   - LAPACK's reflector convention (d/zlarfg): R_jj = -sign(Re x_0) |x| for the column x that is reduced, the diagonal of R_b is
+ *     real (Im R_jj == 0 exactly), and H_j = I (R_jj = x_0, either sign) where x is already reduced (nothing below x_0, x_0 real).
+ *     Q_b has orthonormal columns also for rank-deficient blocks (zero or equal columns).
+ *   - the same call on the same data gives bit-identical Q_b and R_b.
+ *   - n_jobs <= 0: returns 0, nothing is touched.  A job with m <= 0 or n <= 0: TPA_E_BADARG.  m <= 19200 (f64) / 9600 (c128) for
+ *     every job, otherwise TPA_E_BADARG: blocks beyond the row limit of the blocked path go to the one-workgroup kernel, which
+ *     holds a reflector in 150 KB of LDS.  An argument error is found before anything is launched: the outputs are untouched. */
 int tpa_qr_batch(int dtype, const int64_t *jobs_host, int n_jobs, const void *a_base, void *q_base,
                  void *r_base, void *stream);
 /* Test hook: bit 0 = always use the one-workgroup Householder kernel (default: blocked compact-WY QR on the matrix

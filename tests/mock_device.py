@@ -399,11 +399,22 @@ class MockLib:
             VH[v_off:v_off + k * n] = vh.reshape(-1)
         return 0
 
+    def tpa_qr_set_algorithm(self, v):      # test hook of the device dispatch: LAPACK has one path
+        return 0
+
     def tpa_qr_batch(self, code, jobs_p, n_jobs, a_p, q_p, r_p, stream):
+        if code not in (0, 1):
+            return _lib.E_BADARG
+        if n_jobs <= 0:
+            return 0
         dt = _npdt(code)
         jobs = _host(jobs_p, (n_jobs, 8))
-        Q, R = REG.view(q_p, dt), REG.view(r_p, dt)
         isz = np.dtype(dt).itemsize
+        # (TPA_ARG_CHECKs of the entry point, before any device work: empty blocks; blocks beyond the blocked path's row limit go to
+        # the one-workgroup kernel, whose reflector has to fit into 150 KB of LDS)
+        if np.any(jobs[:, 1:3] <= 0) or int(jobs[:, 1].max()) * isz > 150 * 1024:
+            return _lib.E_BADARG
+        Q, R = REG.view(q_p, dt), REG.view(r_p, dt)
         for a_off, m, n, q_off, r_off, _, _, _ in jobs:
             k = min(m, n)
             A = REG.view(a_p + int(a_off) * isz, dt)      # (np_conserved.qr_batched: the blocks of several arenas, offsets from one base address)

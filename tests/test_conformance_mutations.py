@@ -1,12 +1,13 @@
 """Sensitivity of the conformance suite: the numpy emulation is wrapped with ONE deliberate defect at a time and the checkers of
-tests/test_conformance_gemm.py, test_conformance_vec.py and test_conformance_copy.py have to reject every one of them (and accept the
-unbroken emulation on the same cases).  Needs no GPU: this is the evidence that a subtly wrong kernel would not pass."""
+tests/test_conformance_gemm.py, test_conformance_vec.py, test_conformance_copy.py and test_conformance_qr.py have to reject every one
+of them (and accept the unbroken emulation on the same cases).  Needs no GPU: this is the evidence that a subtly wrong kernel would not pass."""
 import itertools
 
 import numpy as np
 import pytest
 
 import conformance_gemm_cases as cg
+import conformance_qr_cases as cq
 import mock_device
 import test_conformance_copy as tc
 import test_conformance_vec as tv
@@ -186,12 +187,136 @@ def _vec_copy_probes():
     return probes
 
 
+# ---- defects of tpa_qr_batch (code, jobs, n_jobs, A, Q, R, stream) and of tpa_svd_batch --------------------------------------
+
+def _qr_blocks(code, jobs_p, n_jobs, a_p, q_p, r_p):
+    """Writable views (A_b, Q_b, R_b, element behind Q_b) per job of a call of the emulation."""
+    dt = np.complex128 if code else np.float64
+    Q, R = mock_device.REG.view(q_p, dt), mock_device.REG.view(r_p, dt)
+    out = []
+    for a_off, m, n, q_off, r_off in mock_device._host(jobs_p, (n_jobs, 8))[:, :5].tolist():
+        k = min(m, n)
+        A = mock_device.REG.view(a_p + a_off * np.dtype(dt).itemsize, dt)
+        A.flags.writeable = True
+        out.append((A[:m * n].reshape(m, n), Q[q_off:q_off + m * k].reshape(m, k), R[r_off:r_off + k * n].reshape(k, n),
+                    Q[q_off + m * k:q_off + m * k + 1]))
+    return out
+
+
+def _qr_with_output(edit, last_block=True):
+    """A defect that shows in the arenas after a correct factorisation: edit(A_b, Q_b, R_b, behind Q_b) per block."""
+    def make(base):
+        def qr(code, jobs_p, n_jobs, a_p, q_p, r_p, stream):
+            rc = base.tpa_qr_batch(code, jobs_p, n_jobs - (0 if last_block else 1), a_p, q_p, r_p, stream)
+            for blk in _qr_blocks(code, jobs_p, n_jobs, a_p, q_p, r_p)[:None if last_block else -1]:
+                edit(*blk)
+            return rc
+        return Mutant(base, tpa_qr_batch=qr)
+    return make
+
+
+def _r_lower_unwritten(a, q, r, behind):
+    r[np.tril_indices(r.shape[0], -1, r.shape[1])] = cq._nan(r.dtype)      # (what the caller's uninitialised memory held)
+
+
+def _write_behind_q(a, q, r, behind):
+    behind[:] = 0
+
+
+def _a_overwritten(a, q, r, behind):
+    a[:r.shape[0]] = r
+
+
+def _q_conjugated(a, q, r, behind):
+    q[:] = q.conj()
+
+
+def _sign_flipped(a, q, r, behind):
+    q[:, 0], r[0] = -q[:, 0], -r[0]
+
+
+def _r_column_perturbed(a, q, r, behind):
+    j = r.shape[1] - 1
+    r[0, j] += 1e-12 * np.linalg.norm(a[:, j])
+
+
+def _q_column_perturbed(a, q, r, behind):
+    q[0, 0] += 1e-13
+
+
+def _qr_unsigned_offsets(base):
+    """a_off taken as unsigned: a block in front of a_base is read from somewhere else (modelled: from unrelated memory)."""
+    def qr(code, jobs_p, n_jobs, a_p, q_p, r_p, stream):
+        jobs = mock_device._host(jobs_p, (n_jobs, 8)).copy()
+        isz = 16 if code else 8
+        keep = []
+        for j in jobs:
+            if j[0] < 0:
+                keep.append(dev.to_device(np.random.default_rng(3).standard_normal(2 * j[1] * j[2] + 2)))
+                j[0] = (keep[-1].data_ptr() + isz - 1 - a_p) // isz
+        return base.tpa_qr_batch(code, jobs.ctypes.data, n_jobs, a_p, q_p, r_p, stream)
+    return Mutant(base, tpa_qr_batch=qr)
+
+
+def _svd_with_output(edit):
+    def make(base):
+        def svd(code, jobs_p, n_jobs, a_p, u_p, s_p, vh_p, *rest):
+            rc = base.tpa_svd_batch(code, jobs_p, n_jobs, a_p, u_p, s_p, vh_p, *rest)
+            _, m, n, _, s_off = mock_device._host(jobs_p, (n_jobs, 8))[0, :5].tolist()
+            edit(mock_device.REG.view(s_p, np.float64)[s_off:s_off + min(m, n)])
+            return rc
+        return Mutant(base, tpa_svd_batch=svd)
+    return make
+
+
+def _s_zero_with_vectors(s):
+    s[cq.SVD_RANK:] = 0          # the values beyond the rank are declared zero, their vectors stay
+
+
+def _s_pair_swapped(s):
+    s[[3, 4]] = s[[4, 3]]
+
+
+QR_DEFECTS = {
+    'qr_lower_triangle_of_r_unwritten': _qr_with_output(_r_lower_unwritten),
+    'qr_one_element_written_behind_q': _qr_with_output(_write_behind_q),
+    'qr_a_overwritten_with_r': _qr_with_output(_a_overwritten),
+    'qr_a_off_taken_as_unsigned': _qr_unsigned_offsets,
+    'qr_q_conjugated': _qr_with_output(_q_conjugated),
+    'qr_sign_of_a_row_of_r_and_column_of_q_flipped': _qr_with_output(_sign_flipped),
+    'qr_trailing_column_misses_a_reflector': _qr_with_output(_r_column_perturbed),
+    'qr_column_of_q_perturbed': _qr_with_output(_q_column_perturbed),
+    'qr_last_block_skipped': _qr_with_output(lambda *blk: None, last_block=False),
+}
+SVD_DEFECTS = {
+    'svd_vector_left_where_s_is_zero': _svd_with_output(_s_zero_with_vectors),
+    'svd_pair_of_s_swapped': _svd_with_output(_s_pair_swapped),
+}
+QR_PROBE_CASES = ('wy_k32_real', 'wy_k32_complex', 'negative_a_off_wy_real', 'negative_a_off_onewg_complex')
+SVD_PROBE_CASES = ('qrp_64x8_real_500x48', 'qrp_256x4_complex_48x1000')
+
+
+def _qr_probe_list():
+    return [(lambda L, c=cq.qr_case(n): cq.check_qr(c, cq.run_qr(c, L=L))) for n in QR_PROBE_CASES]
+
+
+def _svd_probe_list():
+    return [(lambda L, c=cq.svd_case(n): cq.check_svd(c, cq.run_svd(c, L=L))) for n in SVD_PROBE_CASES]
+
+
+def _qr_probes():
+    probes = {name: (make, _qr_probe_list()) for name, make in QR_DEFECTS.items()}
+    probes.update({name: (make, _svd_probe_list()) for name, make in SVD_DEFECTS.items()})
+    return probes
+
+
 DEFECTS = list(GEMM_DEFECTS) + ['tpa_dot_drops_its_last_element', 'copy_conjugation_flag_ignored', 'gather_idx_off_ignored',
-                                'tri_lower_diagonal_not_halved']
+                                'tri_lower_diagonal_not_halved'] + list(QR_DEFECTS) + list(SVD_DEFECTS)
 
 
 def test_defect_list_is_complete():
-    assert len(DEFECTS) == 11 and set(DEFECTS) == set(GEMM_DEFECTS) | set(_vec_copy_probes())
+    assert len(DEFECTS) == 22 and set(DEFECTS) == set(GEMM_DEFECTS) | set(_vec_copy_probes()) | set(QR_DEFECTS) | set(SVD_DEFECTS)
+    assert len(QR_DEFECTS) == 9 and len(SVD_DEFECTS) == 2 and set(_qr_probes()) == set(QR_DEFECTS) | set(SVD_DEFECTS)
 
 
 def test_unbroken_emulation_is_accepted(monkeypatch):
@@ -200,6 +325,8 @@ def test_unbroken_emulation_is_accepted(monkeypatch):
     for make, probes in _vec_copy_probes().values():
         for probe in probes:
             probe(base)
+    for probe in _qr_probe_list() + _svd_probe_list():
+        probe(base)
 
 
 @pytest.mark.parametrize("defect", DEFECTS)
@@ -209,7 +336,7 @@ def test_conformance_detects_mutations(monkeypatch, defect):
         n = _gemm_rejections(GEMM_DEFECTS[defect], base)
         print("MUTATION %s: rejected by %d of %d GEMM cases" % (defect, n, len(gemm_cases())))
     else:
-        make, probes = _vec_copy_probes()[defect]
+        make, probes = (_qr_probes() if defect in QR_DEFECTS or defect in SVD_DEFECTS else _vec_copy_probes())[defect]
         n = sum(_rejected(probe, make(base)) for probe in probes)
         print("MUTATION %s: rejected by %d of %d probes" % (defect, n, len(probes)))
     assert n >= 1, "the conformance checker accepts an emulation with the defect '%s'" % defect
