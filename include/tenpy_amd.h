@@ -77,7 +77,7 @@ int tpa_gemm_chain(int dtype, int cfg, const int64_t *tasks_dev, const int64_t *
  * written to out_dev[0..1] on the stream (no host sync); two identical calls give bit-identical results.
  * n <= 0: tpa_axpy and tpa_scal return 0 without a launch.  tpa_dot, tpa_nrm2sq and tpa_lanczos_update read and write no vector
  * element and post out_dev[0..1] = (0, 0); tpa_lanczos_step posts ab_out[0..1] = (0, 0) and leaves w alone (as for any bsq = 0: no
- * division).  tpa_krylov_combine / tpa_krylov_combine_z return TPA_E_BADARG.
+ * division).  tpa_krylov_combine / tpa_krylov_combine_z return TPA_E_BADARG.  tpa_project_out: see there.
  */
 #define TPA_RED_SCRATCH 4096
 int tpa_axpy(int dtype, int64_t n, double alpha_re, double alpha_im, const void *x_dev,
@@ -102,6 +102,28 @@ int tpa_lanczos_update(int dtype, int64_t n, void *w_dev, double alpha_re, doubl
 int tpa_lanczos_step(int dtype, int64_t n, void *w_dev, const void *v1_dev, const void *v0_dev,
                      const double *bsq_prev_dev, double *ab_out_dev, double *scratch_dev, void *stream);
 
+/* dst = src - sum_{j < m} c_j b_j with c_j = sum_i conj(b_j[i]) src[i]: the projection on the orthogonal complement of m packed
+ * vectors b_j = basis_dev + j * stride (elements of dtype, stride >= n) in ONE call, the coefficients never leaving the device.
+ * Replaces the m (npc.inner, iadd_prefactor_other) pairs of OrthogonalNpcLinearOperator.matvec (linalg/sparse.py:243-255) and of the
+ * re-orthogonalisation of a Lanczos step (krylov_based.py:667-669).  Classical Gram-Schmidt: every c_j is taken from the same src
+ * (the reference's loops are the modified form; the two agree to rounding for orthonormal b_j).
+ *   coeff_dev[2 j], coeff_dev[2 j + 1] = (re, im) of c_j, written on the stream (im = 0 for F64); m <= TPA_PROJECT_MAX.
+ *   dst_dev == src_dev (in place) is allowed; dst must not overlap the basis (TPA_E_BADARG where it does).
+ *   nrm2_out_dev: NULL, or nrm2_out_dev[0..1] = (sum |dst_i|^2, 0) out of the pass that writes dst (deterministic two-pass reduction).
+ *   work_dev: TPA_PROJECT_WORK doubles (TPA_RED_SCRATCH holds the partials of two vectors only).  Nothing outside dst[0:n],
+ *   coeff[0:2m], nrm2_out[0:2] and the work area is written; the basis is only read.  Two identical calls give identical bits.
+ * Traffic: itemsize n (2 m + ceil(m / 8) + 2) bytes (src once per 8 basis vectors for the coefficients, every b_j twice, src and
+ * dst once for the update) against 5 m itemsize n of the dot / axpy sequence.  16-byte loads where basis, src and dst are 16-byte
+ * aligned and, for F64, n and (m > 1) stride are even; 8-byte loads otherwise.
+ * m = 0: dst = src (a copy where the two differ; nothing at all in place without nrm2_out_dev), nrm2 as asked; coeff is not touched.
+ * n <= 0: no kernel is launched, no vector element is read or written; coeff[0:2m] and nrm2_out[0:2] are posted as zeros.
+ * TPA_E_BADARG: dtype, m < 0, m > TPA_PROJECT_MAX, and for m > 0: coeff_dev NULL, or (n > 0) basis_dev NULL or stride < n; for
+ * n > 0: src_dev, dst_dev or work_dev NULL.  Argument errors are found before anything is launched. */
+#define TPA_PROJECT_MAX 64
+#define TPA_PROJECT_WORK (2 * 1024 * (TPA_PROJECT_MAX + 1))
+int tpa_project_out(int dtype, int64_t n, const void *basis_dev, int m, int64_t stride, const void *src_dev, void *dst_dev,
+                    double *coeff_dev, double *nrm2_out_dev, double *work_dev, void *stream);
+
 /* LanczosGroundState.run as ONE host call (krylov_based.py:645-700 `_build_krylov`; the caller keeps the reference's host
  * logic -- tridiagonal eigh :702, `_converged` :713 -- in `cb`).  The matvec is a replayed "program" of cached launches:
  *   ops : HOST int64[n_ops][12] = {kind, cfg, p0, p1, p2, count, a_slot, b_slot, c_slot, max_elems, 0, 0}
@@ -113,6 +135,10 @@ int tpa_lanczos_step(int dtype, int64_t n, void *w_dev, const void *v1_dev, cons
  *                 the program; it enqueues an exchange (RCCL all-gather of the row panels of a sharded matvec) that is
  *                 ordered on the launch stream.  The recurrence, its scalars and the stopping test stay replicated and bit-identical
  *                 on every rank, so all ranks run the same number of steps.
+ *         kind 4: tpa_project_out(dtype, n, basis = A, m = count, stride = p1 (elements), src = B, dst = C, coeff = p0, no norm,
+ *                 work = p0 + 2 count + 2): p0 is a device area of 2 count + 2 + TPA_PROJECT_WORK doubles.  The projector of
+ *                 OrthogonalNpcLinearOperator: in front of the operator's program from slot -1 into a temporary, behind it in place
+ *                 on slot -2.
  *         slots: >= 0 -> bufs[slot] (HOST array of n_bufs device pointers: fixed operands and temporaries), -1 -> the input
  *         vector v_k, -2 -> the output vector w of this matvec.  (p0..p2 are device pointers stored as integers.)
  *   krylov_dev : (N_max + 1) * n elements; on return vectors 0 .. N-1 are the orthonormal Krylov basis (v_0 = psi0 / |psi0|).
@@ -129,6 +155,16 @@ int tpa_lanczos_run(int dtype, int64_t n, const int64_t *ops, int n_ops, void *c
                     void *krylov_dev, const void *psi0_dev, int N_max, double cutoff, int has_shift, double E_shift,
                     double *scalars_dev, double *scratch_dev, tpa_lanczos_callback cb, void *user,
                     int time_gemms, double *info, void *stream);
+/* tpa_lanczos_run with `flags` (tpa_lanczos_run is this call with flags = 0, project_work_dev = NULL).
+ * flags bit 0: full re-orthogonalisation (`reortho` of the reference, krylov_based.py:667-669).  Step k >= 1 becomes
+ *   alpha = Re <w|v_k> ;  w -= alpha v_k ;  tpa_project_out of w against v_0 .. v_{k-1} in place (basis = krylov_dev, stride = n; the
+ *   beta v_{k-1} term of the recurrence is part of that projection) ;  bsq = |w|^2 out of the same pass ;  w /= sqrt(bsq);
+ *   step 0 is the plain step.  Needs N_max <= TPA_PROJECT_MAX and project_work_dev: 2 TPA_PROJECT_MAX + 2 + TPA_PROJECT_WORK doubles
+ *   (only read and written with bit 0).  Other bits: TPA_E_BADARG. */
+int tpa_lanczos_run_ex(int dtype, int64_t n, const int64_t *ops, int n_ops, void *const *bufs, int n_bufs,
+                       void *krylov_dev, const void *psi0_dev, int N_max, double cutoff, int has_shift, double E_shift,
+                       double *scalars_dev, double *scratch_dev, tpa_lanczos_callback cb, void *user,
+                       int time_gemms, double *info, int flags, double *project_work_dev, void *stream);
 /* out = sum_{k < N} coeff[k] v_k over the Krylov basis of tpa_lanczos_run (N <= 64, real coefficients: the eigenvector of
  * the tridiagonal matrix), norm_host[0] = |out| (blocking): `_calc_result_full`, krylov_based.py:223-236, in one pass. */
 int tpa_krylov_combine(int dtype, int64_t n, const void *krylov_dev, int N, const double *coeff, void *out_dev,

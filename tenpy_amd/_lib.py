@@ -14,6 +14,8 @@ from . import _build
 
 F64, C128 = 0, 1
 E_BADARG, E_NOCONV, E_NAN, E_NOMEM, E_RANKCAP = -1, -2, -3, -4, -5
+PROJECT_MAX = 64                              # TPA_PROJECT_MAX
+PROJECT_WORK = 2 * 1024 * (PROJECT_MAX + 1)   # TPA_PROJECT_WORK (doubles)
 
 _lib = None
 
@@ -37,6 +39,10 @@ _SIGS = {
     "tpa_lanczos_step": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tpa_lanczos_run": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int,
                                        ctypes.c_double, ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, _vp, ctypes.c_int, _vp, _vp]),
+    "tpa_lanczos_run_ex": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int,
+                                          ctypes.c_double, ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, _vp, ctypes.c_int, _vp,
+                                          ctypes.c_int, _vp, _vp]),
+    "tpa_project_out": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tpa_lanczos_set_collective": (ctypes.c_int, [COLLECTIVE_CALLBACK, _vp]),
     "tpa_krylov_combine": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tpa_krylov_combine_z": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),

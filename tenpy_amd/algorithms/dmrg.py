@@ -8,6 +8,9 @@ in the reference's order (``prepare_update_local`` -> ``update_local
 
 Options (names as in the reference): ``trunc_params``, ``lanczos_params``, ``chi_list`` (dict sweep -> chi_max);
 ``shard_matvec`` (multi-GPU, ``algorithms/sharded.py``; with ``krylov_row_panels`` the Krylov vectors are row panels), ``profile`` (per-phase timers; synchronises the device).
+
+``orthogonal_to=[MPS, ...]`` (keyword, off by default; not with ``shard_matvec``): the search stays orthogonal to the given states
+(reference ``mps_common.py:521-540``) -- the minimum the GPU tests of the projected Lanczos loop need, not an excited-state engine.
 """
 import pickle
 import gc
@@ -34,9 +37,15 @@ class TwoSiteDMRGEngine:
         from ..linalg import _svd_warm
         return _svd_warm.owner_token(self)
 
-    def __init__(self, psi, model_H, options, resume_data=None):
+    def __init__(self, psi, model_H, options, resume_data=None, orthogonal_to=None):
         if not psi.finite:
             raise ValueError("the stand-alone driver handles finite chains; run TeNPy's engines on the mirror for the rest")
+        self.ortho_to_envs = []
+        if orthogonal_to:
+            if dict(options).get('shard_matvec', False):
+                raise ValueError("orthogonal_to is not available together with shard_matvec")
+            from ..networks.mps import OverlapEnvironment
+            self.ortho_to_envs = [OverlapEnvironment(psi, ket) for ket in orthogonal_to]
         self.psi, self.H = psi, model_H
         self.options = options = dict(options)
         self.trunc_params = dict(options.get('trunc_params', {}))
@@ -134,6 +143,8 @@ class TwoSiteDMRGEngine:
             if eff_H.factored and cache.get(i0) is not None:
                 eff_H._fplans = cache[i0]
         theta = eff_H.combine_theta(psi.get_theta(i0, n=2))
+        if self.ortho_to_envs:
+            eff_H = self._wrap_ortho_eff_H(eff_H, i0, theta.get_leg_labels())
         self._tick('heff')
         if self.shard_matvec and self.options.get('krylov_row_panels', False):
             from .sharded import lanczos_row_panels          # north_star: Krylov vectors as row panels, scalars by all-reduce
@@ -166,6 +177,8 @@ class TwoSiteDMRGEngine:
         psi.set_B(i1, VH.split_legs(['(p1.vR)']).ireplace_label('p1', 'p'), form='B')
         psi.set_SR(i0, S)
         env.invalidate(i0, i1, keep_LP=move_right, keep_RP=not move_right)
+        for o_env in self.ortho_to_envs:
+            o_env.invalidate(i0, i1)
         self._tick('setB')
         us = self.update_stats
         us['i0'].append(i0)
@@ -175,6 +188,20 @@ class TwoSiteDMRGEngine:
         us['err'].append(err.eps)
         us['chi'].append(len(S))
         return err
+
+    def _wrap_ortho_eff_H(self, eff_H, i0, labels):
+        """The statements of the reference's ``_wrap_ortho_eff_H`` (mps_common.py:524-540): the states to stay orthogonal to as
+        vectors of this bond, ``LP . theta_ket . RP`` of the ``<psi|ket>`` environments."""
+        from ..linalg.sparse import OrthogonalNpcLinearOperator
+        ortho_vecs = []
+        for o_env in self.ortho_to_envs:
+            theta = o_env.ket.get_theta(i0, n=2)
+            theta = npc.tensordot(o_env.get_LP(i0, store=True), theta, axes=('vR', 'vL'))
+            theta = npc.tensordot(theta, o_env.get_RP(i0 + 1, store=True), axes=('vR', 'vL'))
+            theta.ireplace_labels(['vR*', 'vL*'], ['vL', 'vR'])
+            theta = eff_H.combine_theta(theta)
+            ortho_vecs.append(theta if list(theta.get_leg_labels()) == list(labels) else theta.transpose(labels))
+        return OrthogonalNpcLinearOperator(eff_H, ortho_vecs)
 
     def _tick(self, phase):
         """Phase timer (the reference's DEBUG_PRINT phases, _npc_helper.pyx:13); synchronises only when profiling."""

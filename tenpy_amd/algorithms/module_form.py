@@ -23,6 +23,7 @@ import warnings
 import numpy as np
 
 from ..linalg import np_conserved as npc
+from ..linalg.charges import DipolarChargeInfo
 from . import mps_common as dev_mc
 
 __all__ = ['device_two_site_h', 'device_one_site_h', 'device_zero_site_h', 'hinted_mixed_svd']
@@ -54,6 +55,11 @@ def device_two_site_h(Ref):
         def _device_ok(env, i0, combine):
             try:
                 if getattr(env, 'has_hc', False) or getattr(env.H, 'explicit_plus_hc', False):
+                    return False
+                if isinstance(env.H.chinfo, DipolarChargeInfo) and not env.ket.finite:
+                    # dipole charges shift from unit cell to unit cell, which update_LP / update_RP below do not do: the reference's class
+                    # (the reference's tests/test_dmrg.py::test_dmrg_dipole_conservation[2-infinite] raised "incompatible LegCharge" in
+                    # update_LP under the fused callers; tests/test_reference_excited_fused.py runs that file)
                     return False
                 LP, RP = env.get_LP(i0), env.get_RP(i0 + 1)
                 if int(np.max(LP.get_leg('vR').get_block_sizes())) < MIN_SECTOR:

@@ -193,7 +193,202 @@ __global__ __launch_bounds__(NT) void scal_rsqrt_dev_kernel(int64_t nd, double *
     for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < nd; i += (int64_t)gridDim.x * NT) x[i] *= f;
 }
 
+// ---- dst = src - sum_j <b_j|src> b_j over m packed vectors (classical Gram-Schmidt, coefficients stay on the device) ---------------
+// What it replaces: the m (npc.inner + iadd_prefactor_other) pairs of OrthogonalNpcLinearOperator.matvec (reference sparse.py:243-255)
+// and of the re-orthogonalisation of a Lanczos step (reference krylov_based.py:667-669) -- m host reads, 5 m itemsize n bytes -- by three passes
+// over itemsize n (2 m + ceil(m / PJ_J) + 2) bytes without a host read.
+// Launch geometry (tests/test_conformance_project.py computes its bounds from these numbers):
+//   item     = 16 bytes (one complex element, or two real ones) in the VEC form -- 16-byte loads and stores; the scalar form (8-byte
+//              loads; item = one element) serves base addresses that are not 16-byte aligned and real data with odd n or odd stride:
+//              every second b_j then starts 8 bytes off a 16-byte boundary (the reason krylov_combine_z_kernel keeps one too).
+//   workgroup= NT = 256 threads, PJ_PER_THREAD = 4 items per thread; grid g = min(PJ_MAXBLK = 1024, ceil(items / 1024)), grid-stride.
+//   pass 1   : grid (g, ceil(m / PJ_J)); a workgroup reads its items of src ONCE for PJ_J = 8 basis vectors and leaves one (re, im)
+//              partial per vector: work[2 (j g + blockIdx.x)].
+//   pass 2   : one workgroup per vector adds its g partials in fixed order (thread t: t, t + 256, ...; then the tree) -> coeff[2 j].
+//   pass 3   : grid g; the m coefficients go to LDS once per workgroup; per item one read of src and of every b_j, a chain of fused
+//              multiply-adds t -= c_j b_j in ascending j, one write of dst; |dst|^2 partials at work[2 PJ_MAXBLK PJ_MAX + 2 blockIdx.x].
+//   pass 4   : reduce_pass2 over the g partials of pass 3 (only with nrm2_out).
+// No floating-point atomics anywhere: the same call on the same data gives the same bits.
+constexpr int PJ_J = 8;
+constexpr int PJ_PER_THREAD = 4;
+constexpr int PJ_MAXBLK = 1024;
+constexpr int PJ_MAX = TPA_PROJECT_MAX;
+static_assert(TPA_PROJECT_WORK >= 2 * PJ_MAXBLK * (PJ_MAX + 1), "TPA_PROJECT_WORK too small for the partials");
+
+template <bool CPLX, bool VEC>
+__device__ __forceinline__ double2 pj_load(const double *p) {
+    if (VEC) return *reinterpret_cast<const double2 *>(p);
+    double2 v;
+    v.x = p[0];
+    v.y = CPLX ? p[1] : 0.;
+    return v;
+}
+
+template <bool CPLX, bool VEC>
+__global__ __launch_bounds__(NT) void project_dots_kernel(int64_t n_items, int m, const double *__restrict__ B, int64_t stride_d,
+                                                          const double *__restrict__ src, double *__restrict__ partial) {
+    __shared__ double red[NT / 64];
+    constexpr int W = (CPLX || VEC) ? 2 : 1;       // doubles per item
+    const int j0 = blockIdx.y * PJ_J;
+    const int nj = (m - j0 < PJ_J) ? m - j0 : PJ_J;
+    const double *Bj = B + (int64_t)j0 * stride_d;
+    double sr[PJ_J], si[PJ_J];
+#pragma unroll
+    for (int jj = 0; jj < PJ_J; ++jj) sr[jj] = si[jj] = 0.;
+    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n_items; i += (int64_t)gridDim.x * NT) {
+        const double2 x = pj_load<CPLX, VEC>(src + W * i);
+#pragma unroll
+        for (int jj = 0; jj < PJ_J; ++jj) {
+            if (jj < nj) {
+                const double2 b = pj_load<CPLX, VEC>(Bj + jj * stride_d + W * i);
+                if (CPLX) {         // conj(b) x
+                    sr[jj] = fma(b.x, x.x, sr[jj]);
+                    sr[jj] = fma(b.y, x.y, sr[jj]);
+                    si[jj] = fma(b.x, x.y, si[jj]);
+                    si[jj] = fma(-b.y, x.x, si[jj]);
+                } else {
+                    sr[jj] = fma(b.x, x.x, sr[jj]);
+                    if (VEC) sr[jj] = fma(b.y, x.y, sr[jj]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int jj = 0; jj < PJ_J; ++jj) {
+        if (jj < nj) {          // (uniform over the workgroup: the barriers of block_sum are reached by all threads or by none)
+            const double r = block_sum<NT>(sr[jj], red);
+            const double im = CPLX ? block_sum<NT>(si[jj], red) : 0.;
+            if (threadIdx.x == 0) {
+                double *p = partial + 2 * ((int64_t)(j0 + jj) * gridDim.x + blockIdx.x);
+                p[0] = r;
+                p[1] = im;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(NT) void project_coeff_kernel(int g, const double *__restrict__ partial, double *__restrict__ coeff) {
+    __shared__ double red[NT / 64];
+    const double *p = partial + 2 * (int64_t)blockIdx.x * g;
+    double sr = 0, si = 0;
+    for (int i = threadIdx.x; i < g; i += NT) {
+        sr += p[2 * i];
+        si += p[2 * i + 1];
+    }
+    sr = block_sum<NT>(sr, red);
+    si = block_sum<NT>(si, red);
+    if (threadIdx.x == 0) {
+        coeff[2 * blockIdx.x] = sr;
+        coeff[2 * blockIdx.x + 1] = si;
+    }
+}
+
+// (src and dst may be the same vector: every item is read and written by the same thread; no __restrict__ on the two)
+template <bool CPLX, bool VEC>
+__global__ __launch_bounds__(NT) void project_update_kernel(int64_t n_items, int m, const double *__restrict__ B, int64_t stride_d,
+                                                            const double *__restrict__ coeff, const double *src, double *dst,
+                                                            double *__restrict__ partial) {
+    __shared__ double red[NT / 64];
+    __shared__ double2 cs[PJ_MAX];
+    constexpr int W = (CPLX || VEC) ? 2 : 1;
+    for (int j = threadIdx.x; j < m; j += NT) cs[j] = double2{coeff[2 * j], coeff[2 * j + 1]};
+    __syncthreads();
+    double s = 0;
+    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < n_items; i += (int64_t)gridDim.x * NT) {
+        double2 t = pj_load<CPLX, VEC>(src + W * i);
+        const double *p = B + W * i;
+#pragma unroll 4
+        for (int j = 0; j < m; ++j) {
+            const double2 c = cs[j];
+            const double2 b = pj_load<CPLX, VEC>(p + j * stride_d);
+            if (CPLX) {
+                t.x = fma(-c.x, b.x, t.x);
+                t.x = fma(c.y, b.y, t.x);
+                t.y = fma(-c.x, b.y, t.y);
+                t.y = fma(-c.y, b.x, t.y);
+            } else {
+                t.x = fma(-c.x, b.x, t.x);
+                if (VEC) t.y = fma(-c.x, b.y, t.y);
+            }
+        }
+        if (VEC) {
+            *reinterpret_cast<double2 *>(dst + W * i) = t;
+        } else {
+            dst[W * i] = t.x;
+            if (CPLX) dst[W * i + 1] = t.y;
+        }
+        s = fma(t.x, t.x, s);
+        if (CPLX || VEC) s = fma(t.y, t.y, s);
+    }
+    if (partial != nullptr) {
+        s = block_sum<NT>(s, red);
+        if (threadIdx.x == 0) {
+            partial[2 * blockIdx.x] = s;
+            partial[2 * blockIdx.x + 1] = 0.;
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int tpa_project_out(int dtype, int64_t n, const void *basis_dev, int m, int64_t stride, const void *src_dev, void *dst_dev,
+                               double *coeff_dev, double *nrm2_out_dev, double *work_dev, void *stream) {
+    TPA_ARG_CHECK(dtype == TPA_F64 || dtype == TPA_C128);
+    TPA_ARG_CHECK(m >= 0 && m <= PJ_MAX);
+    TPA_ARG_CHECK(m == 0 || (coeff_dev != nullptr && (n <= 0 || (basis_dev != nullptr && stride >= n))));
+    TPA_ARG_CHECK(n <= 0 || (src_dev != nullptr && dst_dev != nullptr && work_dev != nullptr));
+    hipStream_t st = (hipStream_t)stream;
+    if (n <= 0) {
+        if (m > 0) TPA_HIP_CHECK(hipMemsetAsync(coeff_dev, 0, sizeof(double) * 2 * m, st));
+        if (nrm2_out_dev) TPA_HIP_CHECK(hipMemsetAsync(nrm2_out_dev, 0, sizeof(double) * 2, st));
+        return 0;
+    }
+    const bool cplx = (dtype == TPA_C128);
+    const int64_t isz = cplx ? 16 : 8;
+    if (m > 0) {        // dst must not overlap the basis
+        const uintptr_t b0 = (uintptr_t)basis_dev, b1 = b0 + (uintptr_t)(((int64_t)(m - 1) * stride + n) * isz);
+        const uintptr_t d0 = (uintptr_t)dst_dev, d1 = d0 + (uintptr_t)(n * isz);
+        TPA_ARG_CHECK((d1 <= b0 || b1 <= d0) && "tpa_project_out: dst overlaps the basis");
+    }
+    const bool aligned = (((uintptr_t)src_dev | (uintptr_t)dst_dev | (m > 0 ? (uintptr_t)basis_dev : 0)) & 15) == 0;
+    const bool vec = aligned && (cplx || (n % 2 == 0 && (m <= 1 || stride % 2 == 0)));
+    const int64_t n_items = (!cplx && vec) ? n / 2 : n;
+    const int64_t stride_d = cplx ? 2 * stride : stride;        // doubles from b_j to b_{j+1}
+    int64_t g64 = (n_items + (int64_t)NT * PJ_PER_THREAD - 1) / ((int64_t)NT * PJ_PER_THREAD);
+    const int g = (int)(g64 > PJ_MAXBLK ? PJ_MAXBLK : g64);
+    const double *B = (const double *)basis_dev, *src = (const double *)src_dev;
+    double *dst = (double *)dst_dev;
+    double *npart = nrm2_out_dev ? work_dev + 2 * (int64_t)PJ_MAXBLK * PJ_MAX : nullptr;
+    if (m == 0 && src == dst && !nrm2_out_dev) return 0;
+    if (m > 0) {
+        const dim3 grid1(g, (m + PJ_J - 1) / PJ_J);
+        if (cplx && vec)
+            project_dots_kernel<true, true><<<grid1, NT, 0, st>>>(n_items, m, B, stride_d, src, work_dev);
+        else if (cplx)
+            project_dots_kernel<true, false><<<grid1, NT, 0, st>>>(n_items, m, B, stride_d, src, work_dev);
+        else if (vec)
+            project_dots_kernel<false, true><<<grid1, NT, 0, st>>>(n_items, m, B, stride_d, src, work_dev);
+        else
+            project_dots_kernel<false, false><<<grid1, NT, 0, st>>>(n_items, m, B, stride_d, src, work_dev);
+        TPA_LAUNCH_CHECK();
+        project_coeff_kernel<<<m, NT, 0, st>>>(g, work_dev, coeff_dev);
+        TPA_LAUNCH_CHECK();
+    }
+    if (cplx && vec)
+        project_update_kernel<true, true><<<g, NT, 0, st>>>(n_items, m, B, stride_d, coeff_dev, src, dst, npart);
+    else if (cplx)
+        project_update_kernel<true, false><<<g, NT, 0, st>>>(n_items, m, B, stride_d, coeff_dev, src, dst, npart);
+    else if (vec)
+        project_update_kernel<false, true><<<g, NT, 0, st>>>(n_items, m, B, stride_d, coeff_dev, src, dst, npart);
+    else
+        project_update_kernel<false, false><<<g, NT, 0, st>>>(n_items, m, B, stride_d, coeff_dev, src, dst, npart);
+    TPA_LAUNCH_CHECK();
+    if (nrm2_out_dev) {
+        reduce_pass2<<<1, NT, 0, st>>>(g, npart, nrm2_out_dev);
+        TPA_LAUNCH_CHECK();
+    }
+    return 0;
+}
 
 extern "C" int tpa_axpy(int dtype, int64_t n, double ar, double ai, const void *x, void *y,
                         void *stream) {
@@ -475,11 +670,49 @@ extern "C" int tpa_lanczos_set_collective(tpa_collective_callback cb, void *user
     return 0;
 }
 
+// Step k >= 1 of the loop with full re-orthogonalisation (flag bit 0; reference krylov_based.py:660-672 with `reortho`):
+//   alpha = Re <w|v_k> ;  w -= alpha v_k ;  w -= sum_{j<k} <v_j|w> v_j (tpa_project_out on the Krylov buffer itself, stride n; the
+//   beta v_{k-1} term of the three-term recurrence is part of that sum) ;  bsq = |w|^2 from the same pass ;  w /= sqrt(bsq).
+// pw: 2 TPA_PROJECT_MAX + 2 + TPA_PROJECT_WORK doubles (coefficients | unused | partials).  ab_out[2] (the alpha slot of the NEXT
+// step, rewritten by it) receives the zero that tpa_project_out posts behind the norm.
+static int lz_step_reortho(int dtype, int64_t n, double *w, const double *V, int k, double *ab_out, double *scratch, double *pw, void *stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const bool cplx = (dtype == TPA_C128);
+    const int64_t nd = cplx ? 2 * n : n;
+    const double *vk = V + (int64_t)k * nd;
+    const int g = grid_for(n, 8);
+    double *part2 = scratch + 2 * MAXBLK;
+    if (!cplx) {
+        reduce_pass1<0><<<g, NT, 0, st>>>(n, w, vk, scratch);
+        reduce_pass2<<<1, NT, 0, st>>>(g, scratch, ab_out);
+        lanczos_update_dev_kernel<false, false><<<g, NT, 0, st>>>(n, w, ab_out, vk, nullptr, nullptr, part2);
+    } else {
+        reduce_pass1<1><<<g, NT, 0, st>>>(n, w, vk, scratch);
+        reduce_pass2<<<1, NT, 0, st>>>(g, scratch, ab_out);
+        lanczos_update_dev_kernel<true, false><<<g, NT, 0, st>>>(n, w, ab_out, vk, nullptr, nullptr, part2);
+    }
+    TPA_LAUNCH_CHECK();
+    if (int rc = tpa_project_out(dtype, n, V, k, n, w, w, pw, ab_out + 1, pw + 2 * PJ_MAX + 2, stream)) return rc;
+    scal_rsqrt_dev_kernel<<<grid_for(nd, 8), NT, 0, st>>>(nd, w, ab_out + 1);
+    TPA_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int tpa_lanczos_run(int dtype, int64_t n, const int64_t *ops, int n_ops, void *const *bufs, int n_bufs,
                                void *krylov_dev, const void *psi0_dev, int N_max, double cutoff, int has_shift, double E_shift,
                                double *scalars_dev, double *scratch_dev, tpa_lanczos_callback cb, void *user,
                                int time_gemms, double *info, void *stream) {
+    return tpa_lanczos_run_ex(dtype, n, ops, n_ops, bufs, n_bufs, krylov_dev, psi0_dev, N_max, cutoff, has_shift, E_shift, scalars_dev,
+                              scratch_dev, cb, user, time_gemms, info, 0, nullptr, stream);
+}
+
+extern "C" int tpa_lanczos_run_ex(int dtype, int64_t n, const int64_t *ops, int n_ops, void *const *bufs, int n_bufs,
+                                  void *krylov_dev, const void *psi0_dev, int N_max, double cutoff, int has_shift, double E_shift,
+                                  double *scalars_dev, double *scratch_dev, tpa_lanczos_callback cb, void *user,
+                                  int time_gemms, double *info, int flags, double *project_work_dev, void *stream) {
     TPA_ARG_CHECK(dtype == TPA_F64 || dtype == TPA_C128);
+    TPA_ARG_CHECK((flags & ~1) == 0 && (!(flags & 1) || (project_work_dev != nullptr && N_max <= PJ_MAX)));
+    const bool reortho = (flags & 1) != 0;
     TPA_ARG_CHECK(n > 0 && N_max >= 1 && n_ops >= 1 && ops != nullptr && krylov_dev != nullptr && psi0_dev != nullptr);
     TPA_ARG_CHECK(scalars_dev != nullptr && scratch_dev != nullptr && cb != nullptr && info != nullptr);
     hipStream_t st = (hipStream_t)stream;
@@ -534,6 +767,10 @@ extern "C" int tpa_lanczos_run(int dtype, int64_t n, const int64_t *ops, int n_o
                     snprintf(tpa_errbuf, sizeof(tpa_errbuf), "tpa_lanczos_run: the collective callback of op %d failed (%d)", o, rc);
                     return TPA_E_BADARG;
                 }
+            } else if (op[0] == 4) {        // dst = src - sum_j <b_j|src> b_j over `count` packed vectors (the projector of an excited-state search)
+                TPA_ARG_CHECK(a != nullptr && b != nullptr && c != nullptr && op[2] != 0 && op[5] >= 0 && op[5] <= PJ_MAX);
+                double *pw = (double *)op[2];
+                if (int rc = tpa_project_out(dtype, n, a, (int)op[5], op[3], b, c, pw, nullptr, pw + 2 * op[5] + 2, stream)) return rc;
             } else {
                 TPA_ARG_CHECK(false && "unknown op kind");
             }
@@ -541,8 +778,10 @@ extern "C" int tpa_lanczos_run(int dtype, int64_t n, const int64_t *ops, int n_o
         ++n_matvec;
         if (has_shift)
             if (int rc = tpa_axpy(dtype, n, E_shift, 0., vin, w, stream)) return rc;
-        if (int rc = tpa_lanczos_step(dtype, n, w, vin, k > 0 ? (const void *)(V + (int64_t)(k - 1) * nd) : nullptr,
-                                      k > 0 ? scalars_dev + 2 * (k - 1) + 1 : nullptr, scalars_dev + 2 * k, scratch_dev, stream))
+        if (reortho && k > 0) {
+            if (int rc = lz_step_reortho(dtype, n, w, V, k, scalars_dev + 2 * k, scratch_dev, project_work_dev, stream)) return rc;
+        } else if (int rc = tpa_lanczos_step(dtype, n, w, vin, k > 0 ? (const void *)(V + (int64_t)(k - 1) * nd) : nullptr,
+                                             k > 0 ? scalars_dev + 2 * (k - 1) + 1 : nullptr, scalars_dev + 2 * k, scratch_dev, stream))
             return rc;
         lz_post_scalars_kernel<<<1, 1, 0, st>>>(scalars_dev + 2 * k, H.pinned + 2 * k);
         TPA_HIP_CHECK(hipEventRecord(H.ev[k], st));

@@ -18,7 +18,7 @@ a TeNPy that keeps its own ``np_conserved`` -- is ``tenpy_amd/_npc_helper.py``.
 ``install(fused=True)`` additionally rebinds, after ``import tenpy``, the callers for which the device has a
 fused form: ``LanczosGroundState`` (one fused recurrence kernel per step instead of four BLAS-1 calls), ``TwoSiteH``
 (cached plans; factored matvec LP . theta . W0 W1 . RP for ``combine=False``), the bond hint of the warm-started block
-SVD, and for TDVP ``LanczosEvolution`` (one native loop and one combination pass per evolution) with the device ``OneSiteH`` /
+SVD, ``OrthogonalNpcLinearOperator`` (the projections of an excited-state search inside the native Krylov loop), and for TDVP ``LanczosEvolution`` (one native loop and one combination pass per evolution) with the device ``OneSiteH`` /
 ``ZeroSiteH``; see :func:`use_fused_callers`.
 """
 import importlib
@@ -111,6 +111,10 @@ def use_fused_callers():
       reference's classes; ``TwoSiteTDVPEngine.EffectiveH`` / ``SingleSiteTDVPEngine.EffectiveH`` (``tdvp.py:248`` / ``:333``) get the
       device ``TwoSiteH`` / ``OneSiteH``, so that the forward evolutions run natively too.  ``OneSiteH`` / ``ZeroSiteH`` are rebound in
       ``mps_common`` and ``tdvp`` only: DMRG, VUMPS and the plane-wave excitations keep theirs.
+    * ``OrthogonalNpcLinearOperator`` (``linalg/sparse.py:220``; constructed at ``mps_common.py:540 _wrap_ortho_eff_H``, where it is
+      imported by name) -> the device class of ``tenpy_amd/linalg/sparse.py`` (same constructor, same ``gram_schmidt``, same
+      ``matvec``), whose ``native_input`` puts the two projections into the launch program of the operator it wraps: the engines'
+      ``orthogonal_to=[...]`` runs (excited states) reach the native Krylov loop through the device ``TwoSiteH``.
     """
     import tenpy.algorithms.dmrg as ref_dmrg
     import tenpy.algorithms.mps_common as ref_mc
@@ -119,6 +123,9 @@ def use_fused_callers():
     from .linalg import krylov_based as kb
     ref_kb.LanczosGroundState = kb.LanczosGroundState
     ref_dmrg.LanczosGroundState = kb.LanczosGroundState
+    import tenpy.linalg.sparse as ref_sparse
+    from .linalg import sparse as dev_sparse
+    ref_sparse.OrthogonalNpcLinearOperator = ref_mc.OrthogonalNpcLinearOperator = dev_sparse.OrthogonalNpcLinearOperator
     if not hasattr(ref_mc.TwoSiteH, '_reference_class'):
         dev_cls = module_form.device_two_site_h(ref_mc.TwoSiteH)
         ref_mc.TwoSiteH = dev_cls

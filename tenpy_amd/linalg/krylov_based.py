@@ -31,7 +31,8 @@ PIPELINED = _os.environ.get('TPA_LANCZOS_PIPELINED', '1') != '0'     # device-re
 __all__ = ['LanczosGroundState', 'LanczosEvolution', 'Arnoldi', 'lanczos', 'gram_schmidt', 'iscale_prefactor', 'iadd_prefactor_other']
 
 
-stats = {'runs': 0, 'n_matvec': 0, 'n_ill_conditioned': 0, 'n_degenerate': 0, 'n_native_sharded': 0, 'n_native_evolve': 0}
+stats = {'runs': 0, 'n_matvec': 0, 'n_ill_conditioned': 0, 'n_degenerate': 0, 'n_native_sharded': 0, 'n_native_evolve': 0,
+         'n_native_ortho': 0, 'n_ortho_declined': 0, 'n_native_reortho': 0}
 
 
 class LanczosGroundState:
@@ -82,8 +83,8 @@ class LanczosGroundState:
     # ---- the whole run as one host call (tpa_lanczos_run) ---------------------------------------------------------
     def _native_program(self):
         """``(ops, bufs, gemm_plans)`` if the operator can hand its matvec over as a launch program (``TwoSiteH.matvec_program``)
-        and the options are the ones the native loop covers (no re-orthogonalisation, all Krylov vectors cached)."""
-        if not (NATIVE and PIPELINED) or self.reortho or self.N_cache < self.N_max or self.N_max + 1 > 64:
+        and the options are the ones the native loop covers (all Krylov vectors cached; ``reortho`` is a flag of the loop)."""
+        if not (NATIVE and PIPELINED) or self.N_cache < self.N_max or self.N_max + 1 > 64:
             return None
         make = getattr(self.H, 'native_input', None)
         if make is None:
@@ -93,6 +94,8 @@ class LanczosGroundState:
             return None
         got = make(w)
         if got is None:
+            return None
+        if self.reortho and len(got[1]) > 3:       # sharded operators: out of scope of the re-orthogonalised loop
             return None
         self.psi0, prog = got          # (possibly theta embedded in the block structure of H theta)
         return prog
@@ -187,11 +190,22 @@ class LanczosGroundState:
             L.tpa_lanczos_set_collective(ccb, None)
             stats['n_native_sharded'] = stats.get('n_native_sharded', 0) + 1
         failure = None
+        flags = int(self.reortho)
+        stats['n_native_reortho'] += flags
+        extended = flags != 0 or bool(np.any(ops[:, 0] == 4))      # plain runs make exactly the call they always made
         try:
-            dev.check(L.tpa_lanczos_run(code, n, ops.ctypes.data, len(ops), ptrs.ctypes.data, len(ptrs), krylov.data_ptr(),
-                                        w._arena.data_ptr(), N_max, float(self._cutoff), int(self.E_shift is not None),
-                                        float(self.E_shift or 0.), scal.data_ptr(), scr.data_ptr(), cb, None, int(timed),
-                                        info.ctypes.data, dev.stream()), "lanczos_run")
+            if not extended:
+                dev.check(L.tpa_lanczos_run(code, n, ops.ctypes.data, len(ops), ptrs.ctypes.data, len(ptrs), krylov.data_ptr(),
+                                            w._arena.data_ptr(), N_max, float(self._cutoff), int(self.E_shift is not None),
+                                            float(self.E_shift or 0.), scal.data_ptr(), scr.data_ptr(), cb, None, int(timed),
+                                            info.ctypes.data, dev.stream()), "lanczos_run")
+            else:
+                pw = dev.scratch('lanczos_project', 2 * _lib.PROJECT_MAX + 2 + _lib.PROJECT_WORK, np.float64) if flags else None
+                dev.check(L.tpa_lanczos_run_ex(code, n, ops.ctypes.data, len(ops), ptrs.ctypes.data, len(ptrs), krylov.data_ptr(),
+                                               w._arena.data_ptr(), N_max, float(self._cutoff), int(self.E_shift is not None),
+                                               float(self.E_shift or 0.), scal.data_ptr(), scr.data_ptr(), cb, None, int(timed),
+                                               info.ctypes.data, flags, pw.data_ptr() if flags else None, dev.stream()),
+                          "lanczos_run_ex")
         except Exception as e:
             if collective is None:
                 raise
@@ -451,6 +465,13 @@ class LanczosEvolution(LanczosGroundState):
         if normalize:
             return result_full, N
         return result_full * (self._psi0_norm * self._result_norm), N
+
+    def _native_program(self):
+        """As for the ground-state search, except that ``reortho`` keeps the step-by-step route here (its results are pinned against
+        the plain native run by tests/test_lanczos_evolution_native.py::test_fallback_routes)."""
+        if self.reortho:
+            return None
+        return super()._native_program()
 
     def _run_native(self, prog, normalize):
         """The Krylov loop of the ground-state search (:meth:`_native_krylov`; the callback dispatches to the ``_calc_result_krylov`` /

@@ -10,7 +10,7 @@ import numpy as np
 from ..linalg import np_conserved as npc
 from ..linalg.charges import LegCharge
 
-__all__ = ['MPS']
+__all__ = ['MPS', 'OverlapEnvironment']
 
 _FORMS = {'A': (1., 0.), 'B': (0., 1.), 'C': (0.5, 0.5), 'G': (0., 0.), 'Th': (1., 1.), None: None}
 
@@ -136,3 +136,55 @@ class MPS:
             B = self.get_B(i, 'B')
             E = npc.tensordot(B.conj(), npc.tensordot(E, B, axes=['vR', 'vL']), axes=(['vL*', 'p*'], ['vR*', 'p']))
         return E.to_ndarray().reshape(-1)[0]
+
+
+class OverlapEnvironment:
+    """``<bra|ket>`` environments of a finite chain in the shape of ``MPOEnvironment``: ``LP[i]`` (labels ``'vR*', 'vR'``) is
+    everything left of site i, ``RP[i]`` (``'vL', 'vL*'``) everything right of it; grown from the nearest stored part by
+    ``npc.tensordot`` on demand (reference ``MPSEnvironment``, networks/mps.py).  The excited-state search of the stand-alone DMRG
+    driver keeps one per state it stays orthogonal to (bra = the state being optimised)."""
+
+    def __init__(self, bra, ket):
+        self.bra, self.ket, self.L = bra, ket, bra.L
+        self._LP = [None] * self.L
+        self._RP = [None] * self.L
+        one = np.ones((1, 1), dtype=np.result_type(bra.dtype, ket.dtype))
+        self._LP[0] = npc.Array.from_ndarray(one, [bra.get_B(0, None).get_leg('vL'), ket.get_B(0, None).get_leg('vL').conj()],
+                                             labels=['vR*', 'vR'])
+        last = self.L - 1
+        self._RP[last] = npc.Array.from_ndarray(one, [ket.get_B(last, None).get_leg('vR').conj(), bra.get_B(last, None).get_leg('vR')],
+                                                labels=['vL', 'vL*'])
+
+    def get_LP(self, i, store=True):
+        i0 = max(j for j in range(i + 1) if self._LP[j] is not None)
+        LP = self._LP[i0]
+        for k in range(i0, i):
+            LP = npc.tensordot(LP, self.ket.get_B(k, 'A'), axes=('vR', 'vL'))
+            LP = npc.tensordot(self.bra.get_B(k, 'A').conj(), LP, axes=(['p*', 'vL*'], ['p', 'vR*']))      # 'vR*', 'vR'
+            if store:
+                self._LP[k + 1] = LP
+        return LP
+
+    def get_RP(self, i, store=True):
+        i0 = min(j for j in range(i, self.L) if self._RP[j] is not None)
+        RP = self._RP[i0]
+        for k in range(i0, i, -1):
+            RP = npc.tensordot(self.ket.get_B(k, 'B'), RP, axes=('vR', 'vL'))
+            RP = npc.tensordot(RP, self.bra.get_B(k, 'B').conj(), axes=(['p', 'vL*'], ['p*', 'vR*']))       # 'vL', 'vL*'
+            if store:
+                self._RP[k - 1] = RP
+        return RP
+
+    def full_contraction(self):
+        """``<bra|ket>`` (both normalised; ``MPS.norm`` is not looked at)."""
+        k = self.L - 1
+        LP = npc.tensordot(self.get_LP(k, store=False), self.ket.get_B(k, 'A'), axes=('vR', 'vL'))
+        LP = npc.tensordot(self.bra.get_B(k, 'A').conj(), LP, axes=(['p*', 'vL*'], ['p', 'vR*']))
+        return LP.to_ndarray().reshape(-1)[0]
+
+    def invalidate(self, i0, i1):
+        """After the bra's tensors of sites i0, i1 changed: drop every stored part that contains one of them."""
+        for j in range(i1, self.L):
+            self._LP[j] = None
+        for j in range(i0, -1, -1):
+            self._RP[j] = None
