@@ -346,26 +346,60 @@ int tpa_qr_batch(int dtype, const int64_t *jobs_host, int n_jobs, const void *a_
 int tpa_qr_set_algorithm(int v);
 
 /* ---- K7: batched Hermitian eigendecomposition (np.linalg.eigh per block, np_conserved.py:5059-5061; `_eig_worker` :5041)
- * jobs : int64[n_jobs][8] = {a_off, n, w_off, v_off, 0,0,0,0} (HOST);  A_b n x n Hermitian row-major (lower triangle read, UPLO = 'L'),
- *   eigenvalues ascending at w_off in w_dev, eigenvectors as COLUMNS of V_b (n x n row-major).
- * Blocks of >= 96 rows: TWO-SIDED block Jacobi on A_b + mu (mu = 2 |A_b|_F) itself -- 32-row blocks, per round one cyclic Jacobi solve
- * of every 64 x 64 diagonal pair block and the two-sided MFMA update S[P, P'] <- Q_P S[P, P'] Q_P'^H, Qtot[P, :] <- Q_P Qtot[P, :];
- * no GEMM over the data, no squared spectrum; stops when no |S_ij| > eps sqrt(n) sqrt(S_ii S_jj) is left (absolute accuracy
- * eps sqrt(n) |A_b|_F, LAPACK's class).  Smaller blocks (and tpa_eigh_set_direct(0)): the one-sided iteration on the rows of A_b + mu.
- * All blocks of the call share the launches: callers batch independent matrices (np_conserved.eigh_batched: the bond matrices of a
- * TEBD half-step).  work_dev >= tpa_eigh_worksize bytes.  Synchronises the stream. */
+ * jobs : int64[n_jobs][8] = {a_off, n, w_off, v_off, 0,0,0,0} (HOST);  A_b n x n row-major, eigenvalues at w_off in w_dev,
+ *   eigenvectors as COLUMNS of V_b (n x n row-major at v_off in v_base).  The three offsets are independent of each other.
+ * Route, chosen PER CALL: if the largest block of the call, padded to an even number of rows, has >= 96 rows, ALL blocks of the call
+ * (1-row blocks included) run the TWO-SIDED block Jacobi on A_b + mu (mu = 2 |A_b|_F) itself -- 32-row blocks, per round one cyclic
+ * Jacobi solve of every 64 x 64 diagonal pair block and the two-sided MFMA update S[P, P'] <- Q_P S[P, P'] Q_P'^H,
+ * Qtot[P, :] <- Q_P Qtot[P, :]; no GEMM over the data, no squared spectrum; it stops when no |S_ij| > 2^-52 sqrt(n) sqrt(S_ii S_jj)
+ * is left.  Otherwise (and with tpa_eigh_set_direct(0), and for real data when the activity-driven rounds are switched off, bit 24 of
+ * tpa_svd_set_algorithm): the one-sided iteration on the rows of A_b + mu.  All blocks of the call share the launches: callers
+ * batch independent matrices (np_conserved.eigh_batched: the bond matrices of a TEBD half-step).
+ * Pinned by tests/test_conformance_eigh.py on every route (two-sided, one-sided below 96 rows, one-sided on the Gram tables):
+ *   - only the LOWER triangle of A_b is read (UPLO = 'L'), and of its diagonal only the real part: what stands above the diagonal
+ *     (NaN, Inf, any finite data) and in Im A_ii has no influence on the result, mu = 2 |A_b|_F of the matrix so defined included.
+ *   - W_b and V_b are written COMPLETELY (w_dev / v_base may be uninitialised memory), nothing outside of them is written, a_base is
+ *     only read.
+ *   - the eigenvalues ascend exactly (w[i + 1] >= w[i]).  Accuracy, in units u = eps sqrt(n) |A_b|_F (eps = 2^-53, f = 4 for complex
+ *     data, |A_b|_F of the matrix defined by the lower triangle).  Every route iterates on A_b + mu, a matrix of norm up to
+ *     (1 + 2 sqrt(n)) |A_b|_F with its spectrum in [|A_b|_F, 3 |A_b|_F]: the absolute accuracy is that of LAPACK's class ON THE SHIFTED
+ *     MATRIX plus what the stopping rule leaves, NOT eps sqrt(n) |A_b|_F (rounds 1 - 6 said so; measured: 30 - 300 u at n = 64 ... 161
+ *     where LAPACK reaches 1 - 2 u):  |w_i - lambda_i| <= (6 n + 16 f (1 + 2 sqrt(n))) u,  |A_b v_i - w_i v_i|_2 <=
+ *     (6 sqrt(n) + 16 f (1 + 2 sqrt(n))) u per vector.  Column norms of V_b^H V_b - I <= 64 f eps sqrt(n) (LAPACK's class, 8 times what
+ *     LAPACK itself reaches).  A diagonal block comes out exactly: w the sorted diagonal, V_b a signed permutation matrix of exact
+ *     0 / +-1.  The iteration runs on the data scaled by a power of two (1 <= 2^-k mu < 2): |A_b|_F from 1e-150 to 1e+150 is fine.
+ *   - the same call on the same data gives bit-identical W and V.
+ *   - n_jobs <= 0: returns 0, nothing is touched.  dtype other than TPA_F64 / TPA_C128, a job with n <= 0, work_bytes <
+ *     tpa_eigh_worksize: TPA_E_BADARG, found before anything is launched.  tpa_eigh_worksize does not depend on the test hooks and is
+ *     > 0 for n_jobs = 0.
+ *   - NaN / Inf in the triangle that is read (or |A_b|_F^2 beyond the range of a double): TPA_E_NAN (-> ValueError, like K5), decided by
+ *     the norm before the iteration starts; max_sweeps exhausted: TPA_E_NOCONV.  In both cases W and V are untouched.
+ * work_dev >= tpa_eigh_worksize bytes.  Synchronises the stream. */
 int64_t tpa_eigh_worksize(int dtype, const int64_t *jobs_host, int n_jobs);
 int tpa_eigh_batch(int dtype, const int64_t *jobs_host, int n_jobs, const void *a_base,
                    double *w_dev, void *v_base, void *work_dev, int64_t work_bytes, int max_sweeps,
                    double tol, int *sweeps_done, void *stream);
 /* Test hook: 0 = tpa_eigh_batch always takes the shift + one-sided route (rounds 1 - 5), 1 = default. */
 int tpa_eigh_set_direct(int on);
+/* Test hook (read-only): 1 if the last tpa_eigh_batch on this host thread ran the direct two-sided iteration, 0 if it ran the
+ * one-sided route (or returned before the iteration). */
+int tpa_eigh_last_direct(void);
 /* Eigenpairs of Hermitian blocks out of their SVDs A_b = U_b S_b VH_b (tpa_svd_batch), WITH the check that this is legitimate: where |lambda|
  * is not shared by a positive and a negative eigenvalue, v_i = d_i u_i (d_i = +/-1), lambda_i = d_i S_i and u_i is the eigenvector.
  * np_conserved.eigh_batched takes this route for real data (the graded, rank-deficient density matrices of the mixer, mps_common.py:1972-2079:
  * ~7 Jacobi sweeps on the rank-r factor instead of 35 - 40 on the matrix) and falls back to tpa_eigh_batch if err is not at rounding level.
- * jobs : int64[n_jobs][8] = {u_off, n, s_off, vh_off, lam_off, 0,0,0} (HOST);  lam_dev[lam_off + i] = d_i S_i (order of S: descending |lambda|),
- * err_dev[job] = max_i S_i |v_i - d_i u_i| = max_i |A u_i - lambda_i u_i|.  Asynchronous on `stream`. */
+ * jobs : int64[n_jobs][8] = {u_off, n, s_off, vh_off, lam_off, 0,0,0} (HOST);  U_b n x n row-major (vectors = columns u_i), VH_b n x n
+ * row-major (rows = v_i^H); all four offsets are independent.  Jobs of different n share the call.
+ * Pinned by tests/test_conformance_eigh.py:
+ *   - d_i = -1 if Re u_i^H v_i < 0, else +1 (a zero or NaN product gives +1);  lam_dev[lam_off + i] = d_i S_i EXACTLY (order of S:
+ *     descending |lambda|); nothing else of lam_dev is written.
+ *   - err_dev[job] = max_i S_i |v_i - d_i u_i|_2 (= max_i |A u_i - lambda_i u_i|), >= 0.  err_dev[0 .. n_jobs) is CLEARED by the call
+ *     (whatever it held: the maximum is taken on bit patterns, which needs the +0.0 start); v_i = d_i u_i bit for bit gives exactly
+ *     0.0, vectors with S_i = 0 contribute 0.  A NaN in u_i, v_i or S_i makes err_dev[job] >= 1e300 (never a value that passes a
+ *     gate), other jobs are unaffected.
+ *   - the same call on the same data gives bit-identical lam and err.
+ *   - n_jobs <= 0: returns 0, nothing is touched.  A bad dtype or a job with n <= 0: TPA_E_BADARG, nothing is launched.
+ * Asynchronous on `stream`. */
 int tpa_eigh_from_svd(int dtype, const int64_t *jobs_host, int n_jobs, const void *u_base, const double *s_dev,
                       const void *vh_base, double *lam_dev, double *err_dev, void *stream);
 

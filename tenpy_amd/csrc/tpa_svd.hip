@@ -1525,6 +1525,7 @@ static thread_local int tpa_svd_strict = 0;
 // |H_ij| <= eps sqrt(n) mu on the shifted matrix: the absolute accuracy class of LAPACK's eigh, as before.
 static thread_local int tpa_svd_direct = 0;        // request (set around svd_run by tpa_eigh_batch)
 static thread_local int tpa_svd_direct_used = 0;   // answer: the call ran the direct iteration (eigenvectors come out on the G side)
+static thread_local int tpa_eigh_last_direct_used = 0;      // tpa_svd_direct_used of the last tpa_eigh_batch on this thread (tpa_eigh_last_direct)
 int tpa_eigh_direct = 1;                           // test hook (TPA_EIGH_DIRECT=0 / tpa_eigh_set_direct): the shift + one-sided SVD route of rounds 1 - 5
 int tpa_svd_dyn_round0 = 1;      // the first round of a sweep adapts to the activity of its pairs (bit 25 of tpa_svd_set_algorithm: off)
 int tpa_svd_dyn = 1;             // 0 (TPA_SVD_DYN=0 / bit 24 of tpa_svd_set_algorithm): the full round-robin schedule in every sweep (rounds 3 - 5)
@@ -2943,12 +2944,24 @@ struct EighJob {  // int64[8]
 constexpr int EIGH_PARTS = 32;      // workgroups per job of the elementwise passes (a batched TEBD call holds ~100 blocks of 1024 x 1024)
 template <bool CPLX>
 __global__ __launch_bounds__(NT) void eigh_fro_kernel(const EighJob *__restrict__ jobs, const double *__restrict__ A, double *__restrict__ fpart) {
+    // |A_b|_F^2 of the matrix eigh_shift_kernel builds (UPLO = 'L'): the strict lower triangle counts twice, the diagonal with its
+    // real part; nothing above the diagonal is read (callers may leave anything there, NaN included)
     __shared__ double red[NT / 64];
     const EighJob J = jobs[blockIdx.y];
-    const int64_t tot = J.n * J.n * (CPLX ? 2 : 1);
+    const int64_t n = J.n;
     const double *a = A + (CPLX ? 2 : 1) * J.a_off;
     double s = 0;
-    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < tot; e += (int64_t)EIGH_PARTS * NT) s = fma(a[e], a[e], s);
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n * n; e += (int64_t)EIGH_PARTS * NT) {
+        const int64_t i = e / n, j = e % n;
+        if (i < j) continue;
+        if (CPLX) {
+            const double2 v = reinterpret_cast<const double2 *>(a)[e];
+            s = (i == j) ? fma(v.x, v.x, s) : fma(2.0 * v.x, v.x, fma(2.0 * v.y, v.y, s));
+        } else {
+            const double v = a[e];
+            s = fma((i == j) ? v : 2.0 * v, v, s);
+        }
+    }
     s = block_sum<NT>(s, red);
     if (threadIdx.x == 0) fpart[blockIdx.y * EIGH_PARTS + blockIdx.x] = s;
 }
@@ -2956,7 +2969,8 @@ __global__ __launch_bounds__(NT) void eigh_fro_kernel(const EighJob *__restrict_
 template <bool CPLX>
 __global__ __launch_bounds__(NT) void eigh_shift_kernel(const EighJob *__restrict__ jobs,
                                                         const double *__restrict__ A, const double *__restrict__ fpart,
-                                                        double *__restrict__ Ap, double *__restrict__ mu) {
+                                                        double *__restrict__ Ap, double *__restrict__ mu,
+                                                        unsigned int *__restrict__ nonfinite) {
     const EighJob J = jobs[blockIdx.y];
     const int64_t n = J.n;
     const double *a = A + (CPLX ? 2 : 1) * J.a_off;
@@ -2965,8 +2979,19 @@ __global__ __launch_bounds__(NT) void eigh_shift_kernel(const EighJob *__restric
     for (int k = 0; k < EIGH_PARTS; ++k) s += fpart[blockIdx.y * EIGH_PARTS + k];      // fixed order: every workgroup gets the same bits
     // mu = 2 ||A||_F (1 if A == 0): spectrum of A' lies in [||A||_F, 3 ||A||_F] > 0, so every singular
     // vector is well defined and the Jacobi iteration sees a condition number <= 3.
-    const double m = (s > 0.0) ? 2.0 * sqrt(s) : 1.0;
-    if (threadIdx.x == 0 && blockIdx.x == 0) mu[blockIdx.y] = m;
+    // A sum that is not finite (NaN / Inf in the triangle that is read, or |A_b|_F^2 beyond the range of a double) is NOT turned into a
+    // shift: it goes to the host (mapped pinned word), which returns TPA_E_NAN before the iteration starts.
+    const double m = (s == 0.0) ? 1.0 : 2.0 * sqrt(s);
+    // The iteration runs on 2^-k (A + mu) with 1 <= 2^-k mu < 2 (an exact scaling; eigh_finish_kernel takes it back): the one-sided
+    // rounds square the squared row norms, which leaves the range of a double for |A_b|_F beyond 1e+-75.
+    const double sc = ldexp(1.0, -ilogb(m));
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        mu[blockIdx.y] = m;
+        if (!(fabs(s) <= 1.7976931348623157e308)) {
+            nonfinite[0] = 1u;
+            __threadfence_system();
+        }
+    }
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n * n; e += (int64_t)EIGH_PARTS * NT) {
         const int64_t i = e / n, j = e % n;
         if (CPLX) {
@@ -2978,11 +3003,13 @@ __global__ __launch_bounds__(NT) void eigh_shift_kernel(const EighJob *__restric
                 v.x += m;
                 v.y = 0;
             }
+            v.x *= sc;
+            v.y *= sc;
             reinterpret_cast<double2 *>(ap)[e] = v;
         } else {
             double v = (i >= j) ? a[i * n + j] : a[j * n + i];
             if (i == j) v += m;
-            ap[e] = v;
+            ap[e] = v * sc;
         }
     }
 }
@@ -2998,8 +3025,9 @@ __global__ __launch_bounds__(NT) void eigh_finish_kernel(const EighJob *__restri
     const EighJob J = jobs[blockIdx.y];
     const int64_t n = J.n;
     const double m = mu[blockIdx.y];
+    const int ex = ilogb(m);      // the iteration ran on 2^-ex (A + mu): eigh_shift_kernel
     if (blockIdx.x == 0)
-        for (int64_t j = threadIdx.x; j < n; j += NT) Wout[J.w_off + j] = S[J.s_off + (n - 1 - j)] - m;
+        for (int64_t j = threadIdx.x; j < n; j += NT) Wout[J.w_off + j] = ldexp(S[J.s_off + (n - 1 - j)] - ldexp(m, -ex), ex);
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n * n; e += (int64_t)gridDim.x * NT) {
         const int64_t i = e / n, j = e % n;
         const int64_t src = from_vh ? (J.ap_off + (n - 1 - j) * n + i) : (J.ap_off + i * n + (n - 1 - j));
@@ -3087,27 +3115,44 @@ extern "C" int tpa_eigh_batch(int dtype, const int64_t *jobs_host, int n_jobs, c
     int direct_req = tpa_eigh_direct;
     if (const char *e = getenv("TPA_EIGH_DIRECT")) direct_req = atoi(e) != 0;
     constexpr int EIGH_FIN_PARTS = EIGH_PARTS;
+    tpa_eigh_last_direct_used = 0;
+    unsigned int *nonfinite = (unsigned int *)pin_stage().take(64, st);      // set by eigh_shift_kernel: the norm of some block is not finite
+    TPA_STAGE_CHECK(nonfinite);
+    nonfinite[0] = 0u;
+    // the norm over the triangle that is read is the detector of non-finite input: nothing depends on what rotations do with NaN
+    auto input_finite = [&]() -> int {
+        TPA_HIP_CHECK(hipStreamSynchronize(st));
+        if (nonfinite[0]) {
+            snprintf(tpa_errbuf, sizeof(tpa_errbuf), "tpa_eigh_batch: NaN/Inf in the lower triangle of a block (or |A|_F^2 overflows)");
+            return TPA_E_NAN;
+        }
+        return 0;
+    };
     if (dtype == TPA_F64) {
         eigh_fro_kernel<false><<<dim3(EIGH_PARTS, n_jobs), NT, 0, st>>>(jobs, (const double *)a_base, fpart);
-        eigh_shift_kernel<false><<<dim3(EIGH_PARTS, n_jobs), NT, 0, st>>>(jobs, (const double *)a_base, fpart, (double *)(work + lay.off_ap), mu);
+        eigh_shift_kernel<false><<<dim3(EIGH_PARTS, n_jobs), NT, 0, st>>>(jobs, (const double *)a_base, fpart, (double *)(work + lay.off_ap), mu, nonfinite);
         TPA_LAUNCH_CHECK();
+        if ((rc = input_finite()) != 0) return rc;
         tpa_svd_strict = 1;
         tpa_svd_direct = direct_req;
         rc = svd_run<false>(slay, n_jobs, work + lay.off_ap, work + lay.off_u, (double *)(work + lay.off_s),
                             work + lay.off_vh, work + lay.off_svd, max_sweeps, sweeps_done, st, 0.0);
         tpa_svd_strict = tpa_svd_direct = 0;
+        tpa_eigh_last_direct_used = tpa_svd_direct_used;
         if (rc != 0) return rc;
         const int fv = tpa_svd_direct_used;
         eigh_finish_kernel<false><<<dim3(EIGH_FIN_PARTS, n_jobs), NT, 0, st>>>(jobs, (const double *)(work + (fv ? lay.off_vh : lay.off_u)), (const double *)(work + lay.off_s), mu, w_dev, (double *)v_base, fv);
     } else {
         eigh_fro_kernel<true><<<dim3(EIGH_PARTS, n_jobs), NT, 0, st>>>(jobs, (const double *)a_base, fpart);
-        eigh_shift_kernel<true><<<dim3(EIGH_PARTS, n_jobs), NT, 0, st>>>(jobs, (const double *)a_base, fpart, (double *)(work + lay.off_ap), mu);
+        eigh_shift_kernel<true><<<dim3(EIGH_PARTS, n_jobs), NT, 0, st>>>(jobs, (const double *)a_base, fpart, (double *)(work + lay.off_ap), mu, nonfinite);
         TPA_LAUNCH_CHECK();
+        if ((rc = input_finite()) != 0) return rc;
         tpa_svd_strict = 1;
         tpa_svd_direct = direct_req;
         rc = svd_run<true>(slay, n_jobs, work + lay.off_ap, work + lay.off_u, (double *)(work + lay.off_s),
                            work + lay.off_vh, work + lay.off_svd, max_sweeps, sweeps_done, st, 0.0);
         tpa_svd_strict = tpa_svd_direct = 0;
+        tpa_eigh_last_direct_used = tpa_svd_direct_used;
         if (rc != 0) return rc;
         const int fv = tpa_svd_direct_used;
         eigh_finish_kernel<true><<<dim3(EIGH_FIN_PARTS, n_jobs), NT, 0, st>>>(jobs, (const double *)(work + (fv ? lay.off_vh : lay.off_u)), (const double *)(work + lay.off_s), mu, w_dev, (double *)v_base, fv);
@@ -3232,6 +3277,11 @@ extern "C" int tpa_eigh_from_svd(int dtype, const int64_t *jobs_host, int n_jobs
 extern "C" int tpa_eigh_set_direct(int on) {
     tpa_eigh_direct = on ? 1 : 0;
     return 0;
+}
+
+/* Test hook (read-only): 1 if the last tpa_eigh_batch on this thread ran the direct two-sided iteration, 0 otherwise. */
+extern "C" int tpa_eigh_last_direct(void) {
+    return tpa_eigh_last_direct_used;
 }
 
 extern "C" int tpa_svd_set_rank_cap(int cap) {

@@ -426,30 +426,65 @@ class MockLib:
     def tpa_eigh_worksize(self, code, jobs_p, n):
         return 256
 
-    def tpa_eigh_set_direct(self, on):
+    def tpa_eigh_set_direct(self, on):      # test hook of the device dispatch: LAPACK has one path; remembered for tpa_eigh_last_direct
+        self.__dict__['_eigh_direct'] = 1 if on else 0
         return 0
 
+    def tpa_eigh_last_direct(self):
+        """What was requested, for calls whose largest block (padded to an even size) has >= 96 rows; 0 below that."""
+        return self.__dict__.get('_eigh_last_direct', 0)
+
     def tpa_eigh_from_svd(self, code, jobs_p, n_jobs, u_p, s_p, vh_p, lam_p, err_p, stream):
+        if code not in (0, 1):
+            return _lib.E_BADARG
+        if n_jobs <= 0:
+            return 0
         dt = _npdt(code)
         jobs = _host(jobs_p, (n_jobs, 8))
+        if np.any(jobs[:, 1] <= 0):
+            return _lib.E_BADARG
         U, VH = REG.view(u_p, dt), REG.view(vh_p, dt)
         S, lam, err = REG.view(s_p, np.float64), REG.view(lam_p, np.float64), REG.view(err_p, np.float64)
+        err[:n_jobs] = 0.
         for b, (u_off, n, s_off, vh_off, lam_off, _, _, _) in enumerate(jobs):
             u = U[u_off:u_off + n * n].reshape(n, n)
             v = VH[vh_off:vh_off + n * n].reshape(n, n).conj().T
             sg = S[s_off:s_off + n].copy()
-            d = np.where(np.real(np.sum(u.conj() * v, axis=0)) < 0, -1., 1.)
-            lam[lam_off:lam_off + n] = d * sg
-            err[b] = np.max(sg * np.linalg.norm(v - u * d[None, :], axis=0)) if n else 0.
+            with np.errstate(invalid='ignore'):
+                d = np.where(np.real(np.sum(u.conj() * v, axis=0)) < 0, -1., 1.)
+                lam[lam_off:lam_off + n] = d * sg
+                e = sg * np.linalg.norm(v - u * d[None, :], axis=0)
+            e[np.isnan(e)] = 1.0e300           # a NaN never passes a gate (and never takes part in a maximum)
+            err[b] = np.max(e)
         return 0
 
     def tpa_eigh_batch(self, code, jobs_p, n_jobs, a_p, w_p, v_p, work_p, wb, max_sweeps, tol, sweeps_p, stream):
+        # (TPA_ARG_CHECKs of the entry point, before any device work)
+        if code not in (0, 1):
+            return _lib.E_BADARG
+        if n_jobs <= 0:
+            return 0
         dt = _npdt(code)
         jobs = _host(jobs_p, (n_jobs, 8))
+        if np.any(jobs[:, 1] <= 0) or wb < self.tpa_eigh_worksize(code, jobs_p, n_jobs):
+            return _lib.E_BADARG
+        self.__dict__['_eigh_last_direct'] = 0
         A, V = REG.view(a_p, dt), REG.view(v_p, dt)
         W = REG.view(w_p, np.float64)
+        herm = []
         for a_off, n, w_off, v_off, _, _, _, _ in jobs:
-            w, v = np.linalg.eigh(A[a_off:a_off + n * n].reshape(n, n), 'L')
+            # UPLO = 'L': the matrix defined by the lower triangle and the real part of the diagonal; nothing else is read
+            a = A[a_off:a_off + n * n].reshape(n, n)
+            low = np.tril(a, -1)
+            h = low + low.conj().T + np.diag(np.diagonal(a).real)
+            with np.errstate(over='ignore', invalid='ignore'):
+                if not np.isfinite(np.sum(np.abs(h) ** 2)):      # the norm is the detector: NaN / Inf in the triangle that is read
+                    return _lib.E_NAN
+            herm.append(h)
+        if (int(jobs[:, 1].max()) + 1) // 2 * 2 >= 96:
+            self.__dict__['_eigh_last_direct'] = self.__dict__.get('_eigh_direct', 1)
+        for (a_off, n, w_off, v_off, _, _, _, _), h in zip(jobs, herm):
+            w, v = np.linalg.eigh(h, 'L')
             W[w_off:w_off + n] = w
             V[v_off:v_off + n * n] = v.reshape(-1)
         return 0

@@ -1,5 +1,6 @@
 """Sensitivity of the conformance suite: the numpy emulation is wrapped with ONE deliberate defect at a time and the checkers of
-tests/test_conformance_gemm.py, test_conformance_vec.py, test_conformance_copy.py and test_conformance_qr.py have to reject every one
+tests/test_conformance_gemm.py, test_conformance_vec.py, test_conformance_copy.py, test_conformance_qr.py and test_conformance_eigh.py
+have to reject every one
 of them (and accept the unbroken emulation on the same cases).  Needs no GPU: this is the evidence that a subtly wrong kernel would not pass."""
 import itertools
 
@@ -7,6 +8,7 @@ import numpy as np
 import pytest
 
 import conformance_gemm_cases as cg
+import conformance_eigh_cases as ce
 import conformance_qr_cases as cq
 import mock_device
 import test_conformance_copy as tc
@@ -310,12 +312,161 @@ def _qr_probes():
     return probes
 
 
+# ---- defects of tpa_eigh_batch (code, jobs, n_jobs, A, W, V, work, work_bytes, max_sweeps, tol, sweeps, stream) and of
+#      tpa_eigh_from_svd (code, jobs, n_jobs, U, S, VH, lam, err, stream) ---------------------------------------------------------
+
+def _eigh_blocks(code, jobs_p, n_jobs, a_p, w_p, v_p):
+    """Writable views (A_b, W_b, V_b, element behind V_b) per job of a call of the emulation."""
+    dt = np.complex128 if code else np.float64
+    A, W, V = mock_device.REG.view(a_p, dt), mock_device.REG.view(w_p, np.float64), mock_device.REG.view(v_p, dt)
+    A.flags.writeable = True
+    return [(A[a_off:a_off + n * n].reshape(n, n), W[w_off:w_off + n], V[v_off:v_off + n * n].reshape(n, n), V[v_off + n * n:v_off + n * n + 1])
+            for a_off, n, w_off, v_off in mock_device._host(jobs_p, (n_jobs, 8))[:, :4].tolist()]
+
+
+def _eigh_with_output(edit, last_block=True):
+    """A defect that shows in the arenas after a correct decomposition: edit(A_b, W_b, V_b, behind V_b) per block."""
+    def make(base):
+        def eigh(code, jobs_p, n_jobs, a_p, w_p, v_p, *rest):
+            rc = base.tpa_eigh_batch(code, jobs_p, n_jobs - (0 if last_block else 1), a_p, w_p, v_p, *rest)
+            for blk in _eigh_blocks(code, jobs_p, n_jobs, a_p, w_p, v_p)[:None if last_block else -1]:
+                edit(*blk)
+            return rc
+        return Mutant(base, tpa_eigh_batch=eigh)
+    return make
+
+
+def _upper_triangle_read(a, w, v, behind):
+    try:
+        w[:], v[:] = np.linalg.eigh(a, 'U')
+    except np.linalg.LinAlgError:          # (LAPACK on NaN)
+        w[:], v[:] = np.nan, np.nan
+
+
+def _descending(a, w, v, behind):
+    w[:], v[:] = w[::-1].copy(), v[:, ::-1].copy()
+
+
+def _vectors_as_rows(a, w, v, behind):
+    v[:] = v.T.copy()
+
+
+def _vectors_conjugated(a, w, v, behind):
+    v[:] = v.conj()
+
+
+def _vectors_swapped(a, w, v, behind):
+    if len(w) >= 2:
+        v[:, [0, 1]] = v[:, [1, 0]]
+
+
+def _eigenvalue_perturbed(a, w, v, behind):
+    w[len(w) // 2] += 1e-12 * np.linalg.norm(ce.lower_hermitian(a))
+
+
+def _vector_perturbed(a, w, v, behind):
+    v[0, 0] += 1e-12
+
+
+def _write_behind_v(a, w, v, behind):
+    behind[:] = 0
+
+
+def _eigh_a_overwritten(a, w, v, behind):
+    a[0, 0] = w[0]
+
+
+def _eigh_w_off_ignored(base):
+    def eigh(code, jobs_p, n_jobs, *rest):
+        jobs = mock_device._host(jobs_p, (n_jobs, 8)).copy()
+        jobs[:, 2] = np.cumsum(jobs[:, 1]) - jobs[:, 1]
+        return base.tpa_eigh_batch(code, jobs.ctypes.data, n_jobs, *rest)
+    return Mutant(base, tpa_eigh_batch=eigh)
+
+
+def _from_svd_with_output(edit):
+    """edit(u_b, s_b, v_b (columns v_i), lam_b, err (the words of all jobs), job index, err before the call)."""
+    def make(base):
+        def from_svd(code, jobs_p, n_jobs, u_p, s_p, vh_p, lam_p, err_p, stream):
+            dt = np.complex128 if code else np.float64
+            R = mock_device.REG
+            U, VH, S, lam, err = R.view(u_p, dt), R.view(vh_p, dt), R.view(s_p, np.float64), R.view(lam_p, np.float64), R.view(err_p, np.float64)
+            before = err[:n_jobs].copy()
+            rc = base.tpa_eigh_from_svd(code, jobs_p, n_jobs, u_p, s_p, vh_p, lam_p, err_p, stream)
+            for j, (uo, n, so, vo, lo) in enumerate(mock_device._host(jobs_p, (n_jobs, 8))[:, :5].tolist()):
+                edit(U[uo:uo + n * n].reshape(n, n), S[so:so + n], VH[vo:vo + n * n].reshape(n, n).conj().T, lam[lo:lo + n], err, j, before)
+            return rc
+        return Mutant(base, tpa_eigh_from_svd=from_svd)
+    return make
+
+
+def _sign_always_plus(u, s, v, lam, err, j, before):
+    lam[:] = s
+
+
+def _err_of_first_64(u, s, v, lam, err, j, before):
+    with np.errstate(invalid='ignore'):
+        e = (s * np.linalg.norm(v - u * np.sign(lam + (lam == 0))[None, :], axis=0))[:64]
+    err[j] = np.max(np.where(np.isnan(e), 1e300, e))
+
+
+def _err_not_cleared(u, s, v, lam, err, j, before):
+    if before[j:j + 1].view(np.uint64)[0] > err[j:j + 1].view(np.uint64)[0]:      # (the maximum is taken on the bit patterns)
+        err[j] = before[j]
+
+
+def _from_svd_vh_not_conjugated(base):
+    def from_svd(code, jobs_p, n_jobs, u_p, s_p, vh_p, *rest):
+        keep = dev.to_device(mock_device.REG.view(vh_p, np.complex128 if code else np.float64).conj())
+        return base.tpa_eigh_from_svd(code, jobs_p, n_jobs, u_p, s_p, keep.data_ptr(), *rest)
+    return Mutant(base, tpa_eigh_from_svd=from_svd)
+
+
+EIGH_DEFECTS = {
+    'eigh_upper_triangle_read': _eigh_with_output(_upper_triangle_read),
+    'eigh_eigenvalues_descending': _eigh_with_output(_descending),
+    'eigh_vectors_as_rows': _eigh_with_output(_vectors_as_rows),
+    'eigh_vectors_conjugated': _eigh_with_output(_vectors_conjugated),
+    'eigh_two_vectors_swapped_without_their_values': _eigh_with_output(_vectors_swapped),
+    'eigh_one_eigenvalue_off_by_1e-12': _eigh_with_output(_eigenvalue_perturbed),
+    'eigh_one_vector_perturbed_by_1e-12': _eigh_with_output(_vector_perturbed),
+    'eigh_w_off_ignored': _eigh_w_off_ignored,
+    'eigh_one_element_written_behind_v': _eigh_with_output(_write_behind_v),
+    'eigh_a_overwritten': _eigh_with_output(_eigh_a_overwritten),
+    'eigh_last_block_skipped': _eigh_with_output(lambda *blk: None, last_block=False),
+}
+FROM_SVD_DEFECTS = {
+    'from_svd_sign_always_plus': _from_svd_with_output(_sign_always_plus),
+    'from_svd_err_over_the_first_64_vectors_only': _from_svd_with_output(_err_of_first_64),
+    'from_svd_err_dev_not_cleared': _from_svd_with_output(_err_not_cleared),
+    'from_svd_vh_not_conjugated': _from_svd_vh_not_conjugated,
+}
+EIGH_PROBE_CASES = ('small_b32', 'small_c')
+
+
+def _eigh_probe_list():
+    return [(lambda L, c=ce.eigh_case(n): ce.check_eigh(c, ce.run_eigh(c, L=L))) for n in EIGH_PROBE_CASES]
+
+
+def _from_svd_probe_list():
+    kinds = [(k, False) for k in ce.FROM_SVD_KINDS_REAL] + [(k, True) for k in ce.FROM_SVD_KINDS_COMPLEX]
+    return [(lambda L, c=ce.from_svd_case(k, cplx): ce.check_from_svd(c, ce.run_from_svd(c, L=L))) for k, cplx in kinds]
+
+
+def _eigh_probes():
+    probes = {name: (make, _eigh_probe_list()) for name, make in EIGH_DEFECTS.items()}
+    probes.update({name: (make, _from_svd_probe_list()) for name, make in FROM_SVD_DEFECTS.items()})
+    return probes
+
+
 DEFECTS = list(GEMM_DEFECTS) + ['tpa_dot_drops_its_last_element', 'copy_conjugation_flag_ignored', 'gather_idx_off_ignored',
-                                'tri_lower_diagonal_not_halved'] + list(QR_DEFECTS) + list(SVD_DEFECTS)
+                                'tri_lower_diagonal_not_halved'] + list(QR_DEFECTS) + list(SVD_DEFECTS) + list(EIGH_DEFECTS) + list(FROM_SVD_DEFECTS)
 
 
 def test_defect_list_is_complete():
-    assert len(DEFECTS) == 22 and set(DEFECTS) == set(GEMM_DEFECTS) | set(_vec_copy_probes()) | set(QR_DEFECTS) | set(SVD_DEFECTS)
+    assert len(DEFECTS) == 37 and set(DEFECTS) == (set(GEMM_DEFECTS) | set(_vec_copy_probes()) | set(QR_DEFECTS) | set(SVD_DEFECTS)
+                                                   | set(EIGH_DEFECTS) | set(FROM_SVD_DEFECTS))
+    assert len(EIGH_DEFECTS) == 11 and len(FROM_SVD_DEFECTS) == 4 and set(_eigh_probes()) == set(EIGH_DEFECTS) | set(FROM_SVD_DEFECTS)
     assert len(QR_DEFECTS) == 9 and len(SVD_DEFECTS) == 2 and set(_qr_probes()) == set(QR_DEFECTS) | set(SVD_DEFECTS)
 
 
@@ -325,7 +476,7 @@ def test_unbroken_emulation_is_accepted(monkeypatch):
     for make, probes in _vec_copy_probes().values():
         for probe in probes:
             probe(base)
-    for probe in _qr_probe_list() + _svd_probe_list():
+    for probe in _qr_probe_list() + _svd_probe_list() + _eigh_probe_list() + _from_svd_probe_list():
         probe(base)
 
 
@@ -336,7 +487,8 @@ def test_conformance_detects_mutations(monkeypatch, defect):
         n = _gemm_rejections(GEMM_DEFECTS[defect], base)
         print("MUTATION %s: rejected by %d of %d GEMM cases" % (defect, n, len(gemm_cases())))
     else:
-        make, probes = (_qr_probes() if defect in QR_DEFECTS or defect in SVD_DEFECTS else _vec_copy_probes())[defect]
+        make, probes = (_qr_probes() if defect in QR_DEFECTS or defect in SVD_DEFECTS else
+                        _eigh_probes() if defect in EIGH_DEFECTS or defect in FROM_SVD_DEFECTS else _vec_copy_probes())[defect]
         n = sum(_rejected(probe, make(base)) for probe in probes)
         print("MUTATION %s: rejected by %d of %d probes" % (defect, n, len(probes)))
     assert n >= 1, "the conformance checker accepts an emulation with the defect '%s'" % defect
