@@ -139,6 +139,9 @@ int tpa_project_out(int dtype, int64_t n, const void *basis_dev, int m, int64_t 
  *                 work = p0 + 2 count + 2): p0 is a device area of 2 count + 2 + TPA_PROJECT_WORK doubles.  The projector of
  *                 OrthogonalNpcLinearOperator: in front of the operator's program from slot -1 into a temporary, behind it in place
  *                 on slot -2.
+ *         kind 5: {5, 0, jobs, terms, coeff, n_jobs, a_slot, max_d, c_slot, max_elems, 0, 0} -- tpa_mpo_apply_batch(dtype, jobs = p0,
+ *                 n_jobs = count, terms = p1, coeff = p2, max_d (in the place of b_slot), max_elems, src = A, dst = C): the MPO step of
+ *                 a factored operator whose MPO blocks are small matrices.  Not counted as GEMM time.
  *         slots: >= 0 -> bufs[slot] (HOST array of n_bufs device pointers: fixed operands and temporaries), -1 -> the input
  *         vector v_k, -2 -> the output vector w of this matvec.  (p0..p2 are device pointers stored as integers.)
  *   krylov_dev : (N_max + 1) * n elements; on return vectors 0 .. N-1 are the orthonormal Krylov basis (v_0 = psi0 / |psi0|).
@@ -199,6 +202,27 @@ int tpa_copy_batch(int dtype, const int64_t *jobs_dev, int n_jobs, int64_t max_j
  * terms: int64[n_terms][4] = {src_off, src_ld, alpha_re, alpha_im}  (alpha_* are the IEEE-754 bit patterns of doubles) */
 int tpa_lincomb_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const int64_t *terms_dev, int64_t max_job_elems,
                       const void *src_base, void *dst_base, void *stream);
+/* dst slab (pre, d_out, post) = sum_t M_t applied on the middle index of src_t slab (pre, d_in_t, post), batched: the MPO step of
+ * the factored effective Hamiltonians for MPO tensors whose bond legs have 1-wide blocks while a physical charge sector holds
+ * several states -- the W0 / W1 tensordots of TwoSiteH.matvec (mps_common.py:1321-1348) and the W0 tensordot of OneSiteH.matvec
+ * (:1146-1149) as ONE pass; tpa_lincomb_batch is the d = 1 case with the coefficient stored in the term.
+ * jobs : int64[n_jobs][8]  = {dst_off, pre, d_out, post, term_begin, term_count, 0, 0}
+ * terms: int64[n_terms][4] = {src_off, d_in, coeff_off, 0}
+ *   dst[dst_off + (i*d_out + o)*post + j] = sum_t sum_c coeff[coeff_off_t + o*d_in_t + c] * src[src_off_t + (i*d_in_t + c)*post + j]
+ *                                           for i < pre, o < d_out, j < post
+ * Offsets in elements of dtype; coeff_dev holds elements of dtype, row-major d_out x d_in_t per term.  max_d >= every d_in / d_out of
+ * the call (it selects the register budget of the kernel; rows o >= max_d of a job that breaks this are not written); max_job_elems =
+ * max pre * d_out * post sizes the grid, capped at 512 workgroups per job (larger jobs loop).  One job per blockIdx.y like the other
+ * batched entry points of this section: n_jobs <= 0 returns 0 without a launch, n_jobs > 65535 returns TPA_E_BADARG; jobs with a zero
+ * extent do nothing.  dtype and 1 <= max_d <= TPA_MPO_APPLY_MAXD are checked first (TPA_E_BADARG also for n_jobs <= 0), all argument
+ * errors before anything is launched.  A job with term_count = 0 writes zeros.  Every element of a destination slab is written
+ * exactly once, nothing else is written; src and dst must not overlap.  Summation order: terms in table order, c ascending, one chain
+ * of fused multiply-adds per component (real: sum_t d_in_t, complex: twice that) -- two identical calls give identical bits.
+ * Traffic: itemsize (sum_terms pre d_in post + sum_jobs pre d_out post) bytes.  16-byte loads and stores where src_base and dst_base
+ * are 16-byte aligned and, for F64, post, dst_off and every src_off of the job are even; 8-byte ones otherwise. */
+#define TPA_MPO_APPLY_MAXD 16
+int tpa_mpo_apply_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const int64_t *terms_dev, const void *coeff_dev, int max_d,
+                        int64_t max_job_elems, const void *src_base, void *dst_base, void *stream);
 /* x_b[i, j, l] *= s[s_off_b + j]  for each block b viewed as (pre, len, post).  Replaces
  * iscale_axis, np_conserved.py:2132-2140.  jobs: int64[n][6] = {x_off, pre, len, post, s_off, 0};
  * the scale vector s is real (F64) or of `dtype` when s_is_complex. */

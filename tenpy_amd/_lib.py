@@ -16,6 +16,7 @@ F64, C128 = 0, 1
 E_BADARG, E_NOCONV, E_NAN, E_NOMEM, E_RANKCAP = -1, -2, -3, -4, -5
 PROJECT_MAX = 64                              # TPA_PROJECT_MAX
 PROJECT_WORK = 2 * 1024 * (PROJECT_MAX + 1)   # TPA_PROJECT_WORK (doubles)
+MPO_APPLY_MAXD = 16                           # TPA_MPO_APPLY_MAXD
 
 _lib = None
 
@@ -48,6 +49,7 @@ _SIGS = {
     "tpa_krylov_combine_z": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
     "tpa_copy_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp]),
     "tpa_lincomb_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp, _vp]),
+    "tpa_mpo_apply_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp]),
     "tpa_svd_dyn_stats": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "tpa_tri_lower_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int64, _vp, _vp]),
     "tpa_scale_axis_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp]),

@@ -7,13 +7,16 @@
   ``update_LP`` / ``update_RP`` :1421-1437, ``LHeff`` / ``RHeff`` for the mixers :1887-1898) on top of
   ``tenpy_amd.algorithms.mps_common.TwoSiteH``: cached contraction plans, fused ``LHeff`` build, and -- for
   ``combine=False``, the reference's default -- the factored matvec ``LP . theta . (W0 W1) . RP`` with the MPO tensors
-  applied as block-level linear combinations instead of K = 1 GEMMs.  Bonds the device form does not cover (small sectors,
-  MPOs with non-scalar blocks, ``H + h.c.`` environments, exact diagonalisation of small bonds) get the reference's own
-  class: ``__new__`` dispatches, so the engines see one ``EffectiveH``.
+  applied blockwise -- linear combinations of blocks where every MPO block is a single number, small dense matrices on the
+  physical index where a charge sector of the site holds several states (``mps_common.MpoBlockApplyPlan``) -- instead of K = 1
+  GEMMs.  Bonds the device form does not cover (sectors below ``MIN_SECTOR``, MPOs without a conserved charge, MPO bond legs with blocks wider than 1
+  -- MPOs after ``sort_legcharges`` --, physical sectors wider than ``TPA_MPO_APPLY_MAXD`` (two sites: their product),
+  ``H + h.c.`` environments, exact diagonalisation of small bonds) get the reference's own class: ``__new__`` dispatches, so the
+  engines see one ``EffectiveH``.
 * ``device_one_site_h(RefOneSiteH)`` / ``device_zero_site_h(RefZeroSiteH)`` -> the same for the operators TDVP constructs after
   every two-site / one-site update (``tdvp.py:308 one_site_update``, ``:419 zero_site_update``) on top of
-  ``mps_common.OneSiteH`` / ``ZeroSiteH``; ``combine=True``, ``H + h.c.`` environments, MPO blocks that are not single numbers
-  and non-standard labels get the reference's class.
+  ``mps_common.OneSiteH`` / ``ZeroSiteH``; ``combine=True``, ``H + h.c.`` environments, MPO tensors without a blockwise form
+  (``mps_common._mpo_plan_class``: as above) and non-standard labels get the reference's class.
 * ``hinted_mixed_svd(ref_mixed_svd)`` wraps ``TwoSiteDMRGEngine.mixed_svd`` (``dmrg.py:876``) to tell the block SVD which
   bond it decomposes (``np_conserved.svd_hint``), which enables the warm start of ``linalg/_svd_warm.py``.
 """
@@ -66,7 +69,7 @@ def device_two_site_h(Ref):
                     return False
                 if sorted(LP.get_leg_labels()) != sorted(['vR*', 'wR', 'vR']) or sorted(RP.get_leg_labels()) != sorted(['wL', 'vL', 'vL*']):
                     return False
-                if not combine:         # factored form: every block of W0, W1 a single number, no transposed copies needed
+                if not combine:         # factored form: W0, W1 applied blockwise (single numbers or small matrices), no transposed copies needed
                     return dev_mc.factored_matvec_possible(LP, RP, env.H.get_W(i0), env.H.get_W(i0 + 1))
                 return True
             except Exception:
@@ -148,7 +151,7 @@ def device_one_site_h(Ref):
             if combine or not _plain_env(env):
                 return None
             LP, W0, RP = env.get_LP(i0), env.H.get_W(i0), env.get_RP(i0)
-            if list(W0.get_leg_labels()) != ['wL', 'wR', 'p', 'p*'] or dev_mc._mpo_entries(W0) is None or not dev_mc._envs_factorable(LP, RP):
+            if list(W0.get_leg_labels()) != ['wL', 'wR', 'p', 'p*'] or not dev_mc._envs_factorable(LP, RP) or dev_mc._mpo_plan_class(W0) is None:
                 return None
             return LP, W0, RP
 

@@ -11,7 +11,8 @@ MI355X-first differences:
   RHeff = [wL, (p1*.vL), (p1.vL*)];
 * both contraction plans are built once per bond and replayed for every Lanczos step: one matvec is
   exactly two grouped-GEMM launches, no host planning, no allocation besides the result arena;
-* ``factored`` mode (default when every block of W0, W1 is a single number): the same operator applied as
+* ``factored`` mode (default when every block of W0, W1 is a single number, or a small matrix on the physical index between 1-wide
+  blocks of the MPO bond legs -- sites with several states per charge sector): the same operator applied as
   ``LP . theta . (W0 W1) . RP`` -- two GEMM launches with a factor d fewer flops (the physical legs are not fused into
   the contracted index) plus one block-level linear combination for the two MPO tensors; LHeff / RHeff are then only
   built on demand (mixer, tests).  theta stays in its un-fused form (vL, p0, p1, vR) during the Lanczos iteration and
@@ -32,6 +33,10 @@ FACTORED_MATVEC = _os.environ.get('TPA_FACTORED_MATVEC', '1') != '0'   # tuning 
 # compute bound (Heisenberg chi=2048: 0.80 vs 1.37 ms per matvec) and loses when they are launch bound (chi=256: 0.75 vs
 # 0.54 s per sweep; Hubbard ladder chi=1024 with sectors <= 100 wide: 3.7 vs 1.5 s).  Automatic choice: largest bond sector.
 FACTORED_MIN_SECTOR = 200
+# MPO tensors whose physical charge sectors hold several states (MPO bond legs still 1-wide): the MPO step of the factored forms as
+# small dense matrices on the physical index (``MpoBlockApplyPlan``, tpa_mpo_apply_batch).  A/B knob: '0' = the routing without it.
+BLOCK_APPLY = _os.environ.get('TPA_MPO_BLOCK_APPLY', '1') != '0'
+from .._lib import MPO_APPLY_MAXD      # noqa: E402  (TPA_MPO_APPLY_MAXD)
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Fused construction of LHeff / RHeff:  LP.W0 (resp. W1.RP) + combine_legs in ONE kernel launch.
@@ -362,6 +367,196 @@ class MpoApplyPlan:
                                               self.max_elems, X._arena.data_ptr(), res._arena.data_ptr(), dev.stream()), "lincomb")
         return res
 
+    def program_op(self, a_slot, c_slot):
+        """The row of a ``tpa_lanczos_run`` program that applies this plan from slot ``a_slot`` into slot ``c_slot`` (kind 1)."""
+        return [1, 0, self.jobs_dev.data_ptr(), self.terms_dev.data_ptr(), 0, self.n_jobs, a_slot, 0, c_slot, self.max_elems, 0, 0]
+
+
+def _mpo_blocks(W):
+    """(qdata, host copies of the stored blocks) of an MPO tensor whose two MPO bond legs have 1-wide blocks and whose physical charge
+    sectors are at most ``TPA_MPO_APPLY_MAXD`` wide, else ``None`` (cached on W like ``_tpa_entries``).  MPOs without a conserved
+    charge are out of scope whatever the blocking of their legs (no charge rule to select the terms: the reference's contractions)."""
+    blk = getattr(W, '_tpa_blocks', False)
+    if blk is False:
+        labels = list(W.get_leg_labels())
+        blk = None
+        if W.rank == 4 and 'wL' in labels and 'wR' in labels and W.stored_blocks > 0 and W.chinfo.qnumber > 0:
+            phys = [a for a in range(4) if labels[a] not in ('wL', 'wR')]
+            if all(np.all(W.get_leg(l).get_block_sizes() == 1) for l in ('wL', 'wR')) and \
+                    all(int(np.max(W.legs[a].get_block_sizes())) <= MPO_APPLY_MAXD for a in phys):
+                blk = (np.array(W._qdata), [np.array(b) for b in W._data])
+        W._tpa_blocks = blk
+    return blk
+
+
+def _share_mpo_tables(W_new, W):
+    """Hand the host tables cached on the MPO's own tensor ``W`` to its relabelled copy ``W_new`` (one D2H read per site and run)."""
+    W_new._tpa_entries = _mpo_entries(W)
+    if W_new._tpa_entries is None and BLOCK_APPLY and dev.lib_provides('tpa_mpo_apply_batch'):
+        W_new._tpa_blocks = _mpo_blocks(W)
+
+
+def _phys_width(W):
+    return max(int(np.max(leg.get_block_sizes())) for leg, l in zip(W.legs, W.get_leg_labels()) if l not in ('wL', 'wR'))
+
+
+def _mpo_plan_class(W, W2=None):
+    """The plan class that applies the MPO tensor ``W`` (with ``W2``: both neighbours in one pass) to the blocks of a tensor:
+    ``MpoApplyPlan`` when every stored block is a single number, ``MpoBlockApplyPlan`` when the MPO bond legs have 1-wide blocks and
+    the physical sectors (two sites: their products) are at most ``TPA_MPO_APPLY_MAXD`` wide and the installed library provides
+    ``tpa_mpo_apply_batch``; ``None`` when there is no blockwise form."""
+    if _mpo_entries(W) is not None and (W2 is None or _mpo_entries(W2) is not None):
+        return MpoApplyPlan
+    if not BLOCK_APPLY or not dev.lib_provides('tpa_mpo_apply_batch'):
+        return None
+    if _mpo_blocks(W) is None or (W2 is not None and _mpo_blocks(W2) is None):
+        return None
+    if _phys_width(W) * (1 if W2 is None else _phys_width(W2)) > MPO_APPLY_MAXD:
+        return None
+    return MpoBlockApplyPlan
+
+
+class MpoBlockApplyPlan:
+    """``MpoApplyPlan`` for MPO tensors whose physical charge sectors hold several states (MPO bond legs still with 1-wide blocks):
+    only the 1-wide ``w`` leg changes its position, so a block of X ``(.., w, p [, p2], ..)`` is ``(pre, D_in, post)`` in memory and
+    the block of Y it feeds is ``(pre, D_out, post)`` (two sites: ``D = d0 d1``) -- every block of Y is a sum of small dense matrices
+    applied on the physical index of blocks of X.  One ``tpa_mpo_apply_batch`` launch.  With ``W2`` the matrix of a
+    ``(w_in, w_out, sectors)`` term is ``sum_w'' W[w_in, w''] (x) W2[w'', w_out]``, formed once on the host; terms whose matrix is
+    exactly zero are dropped.  Arguments and attributes: see ``MpoApplyPlan``."""
+    _cache = {}
+
+    @classmethod
+    def get(cls, X, W, *args, W2=None, **kwargs):
+        """Cached constructor: the plan depends on the block structure of X and on the MPO tensors only."""
+        b1, b2 = _mpo_blocks(W), (None if W2 is None else _mpo_blocks(W2))
+        key = (X._struct_key(), str(X.dtype), id(b1), None if b2 is None else id(b2), args,
+               tuple(sorted(kwargs.items())), tuple(X.get_leg_labels()))
+        plan = cls._cache.get(key)
+        if plan is None or plan._blocks_alive[0] is not b1 or plan._blocks_alive[1] is not b2:
+            if len(cls._cache) > 4096:
+                cls._cache.clear()
+            plan = cls._cache[key] = cls(X, W, *args, W2=W2, **kwargs)
+            plan._blocks_alive = (b1, b2)       # the key holds id()s: see MpoApplyPlan.get
+        return plan
+
+    @staticmethod
+    def _entries(W, w_in, w_out, p_out, p_in):
+        """keys (w_in, w_out, p_out sector, p_in sector) and the (d_out, d_in) matrices of the stored blocks of ``W``."""
+        wq, blocks = _mpo_blocks(W)
+        wl = list(W.get_leg_labels())
+        ax = [wl.index(w_in), wl.index(w_out), wl.index(p_out), wl.index(p_in)]
+        mats = [np.transpose(b, ax).reshape(b.shape[ax[2]], b.shape[ax[3]]) for b in blocks]
+        return wq[:, ax], mats
+
+    def __init__(self, X, W, x_w, x_p, w_in, w_out, p_out, p_in, out_labels, W2=None, x_p2=None, p2_out=None, p2_in=None):
+        keys, mats = self._entries(W, w_in, w_out, p_out, p_in)
+        xa_w, xa_p = X.get_leg_index(x_w), X.get_leg_index(x_p)
+        xa_p2 = None if W2 is None else X.get_leg_index(x_p2)
+        assert np.all(X.legs[xa_w].get_block_sizes() == 1)
+        rest = [a for a in range(X.rank) if a != xa_w]      # memory order of a block (the w leg has extent 1)
+        if W2 is not None:
+            assert rest.index(xa_p2) == rest.index(xa_p) + 1, "the two physical legs must be neighbours in memory"
+            keys2, mats2 = self._entries(W2, w_in, w_out, p2_out, p2_in)
+            joined = {}
+            for k1, m1 in zip(keys.tolist(), mats):         # join over the common MPO bond, in table order
+                for k2, m2 in zip(keys2.tolist(), mats2):
+                    if k1[1] == k2[0]:
+                        k = (k1[0], k2[1], k1[2], k1[3], k2[2], k2[3])
+                        m = np.kron(m1, m2)
+                        joined[k] = joined[k] + m if k in joined else m
+            kept = sorted(k for k, m in joined.items() if np.any(m != 0))
+            keys = np.array(kept, dtype=np.int64).reshape(-1, 6)
+            mats = [joined[k] for k in kept]
+        else:
+            keep = [n for n, m in enumerate(mats) if np.any(m != 0)]
+            keys, mats = keys[keep], [mats[n] for n in keep]
+        self.dtype = np.result_type(X.dtype, W.dtype) if W2 is None else np.result_type(X.dtype, W.dtype, W2.dtype)
+        self.qtotal = X.chinfo.make_valid(X.qtotal + W.qtotal + (0 if W2 is None else W2.qtotal))
+        legs, labels = list(X.legs), list(X.get_leg_labels())
+        legs[xa_w], labels[xa_w] = (W if W2 is None else W2).get_leg(w_out), w_out
+        legs[xa_p], labels[xa_p] = W.get_leg(p_out), p_out
+        if W2 is not None:
+            legs[xa_p2], labels[xa_p2] = W2.get_leg(p2_out), p2_out
+        perm = [labels.index(l) for l in out_labels]
+        assert [a for a in perm if a != xa_w] == rest, "out_labels must keep the order of the legs other than the MPO leg"
+        self.legs = [legs[a] for a in perm]
+        self.labels = list(out_labels)
+        xq = X._qdata
+        match = np.zeros((len(xq), 0), dtype=bool)
+        if len(keys):
+            match = (xq[:, xa_w][:, None] == keys[None, :, 0]) & (xq[:, xa_p][:, None] == keys[None, :, 3])
+            if W2 is not None:
+                match &= (xq[:, xa_p2][:, None] == keys[None, :, 5])
+        ib, ie = np.nonzero(match)
+        self.empty = len(ib) == 0
+        if self.empty:
+            return
+        oq = xq[ib].copy()
+        oq[:, xa_w], oq[:, xa_p] = keys[ie, 1], keys[ie, 2]
+        if W2 is not None:
+            oq[:, xa_p2] = keys[ie, 4]
+        oq = oq[:, perm]
+        uq, inv = np.unique(oq, axis=0, return_inverse=True)
+        inv = inv.reshape(-1)
+        order = np.lexsort(uq.T)
+        rank_of = np.empty(len(order), dtype=np.int64)
+        rank_of[order] = np.arange(len(order))
+        self.qdata = np.ascontiguousarray(uq[order], dtype=np.intp)
+        blk = rank_of[inv]
+        proto = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
+        sizes = proto._set_blocks(self.qdata, arena=dev.empty(0, self.dtype), qdata_sorted=True)
+        self.offsets = proto._offsets
+        self.total = int(np.sum(sizes))
+        # coefficient table: the matrices back to back, row-major (d_out, d_in)
+        m_shape = np.array([m.shape for m in mats], dtype=np.int64)
+        m_off = np.concatenate([[0], np.cumsum(m_shape[:, 0] * m_shape[:, 1])])
+        coeff = np.concatenate([np.asarray(m, dtype=self.dtype).reshape(-1) for m in mats])
+        shapes_x, sizes_x = X._block_shapes(), X._block_sizes_flat()
+        lead = rest[:rest.index(xa_p)]
+        pre = np.prod(shapes_x[:, lead], axis=1) if lead else np.ones(len(xq), dtype=np.int64)
+        d_in = m_shape[:, 1]
+        post = sizes_x // (pre * shapes_x[:, xa_p] * (1 if W2 is None else shapes_x[:, xa_p2]))
+        assert np.array_equal(pre[ib] * d_in[ie] * post[ib], sizes_x[ib])
+        key = np.lexsort((np.arange(len(blk)), blk))        # one job per block of Y, its terms in a fixed order
+        b_sorted = blk[key]
+        first = np.concatenate([[True], b_sorted[1:] != b_sorted[:-1]])
+        starts = np.nonzero(first)[0]
+        counts = np.diff(np.concatenate([starts, [len(key)]]))
+        kf = key[starts]
+        jobs = np.zeros((len(starts), 8), dtype=np.int64)
+        jobs[:, 0], jobs[:, 1], jobs[:, 2], jobs[:, 3] = self.offsets[b_sorted[starts]], pre[ib[kf]], m_shape[ie[kf], 0], post[ib[kf]]
+        jobs[:, 4], jobs[:, 5] = starts, counts
+        assert np.array_equal(jobs[:, 1] * jobs[:, 2] * jobs[:, 3], sizes[b_sorted[starts]])
+        terms = np.zeros((len(key), 4), dtype=np.int64)
+        terms[:, 0], terms[:, 1], terms[:, 2] = X._offsets[ib[key]], d_in[ie[key]], m_off[ie[key]]
+        assert len(jobs) <= 60000
+        self.jobs_host, self.terms_host, self.coeff_host, self.sizes = jobs, terms, coeff, sizes
+        self.jobs_dev, self.terms_dev, self.coeff_dev = dev.to_device(jobs), dev.to_device(terms), dev.to_device(coeff)
+        self.n_jobs, self.max_elems = len(jobs), int(np.max(sizes[b_sorted[starts]]))
+        self.max_d = int(max(np.max(jobs[:, 2]), np.max(terms[:, 1])))
+        assert self.max_d <= MPO_APPLY_MAXD
+        self.x_key = X._struct_key()
+        self.bytes = 8 * (2 if self.dtype.kind == 'c' else 1) * (self.total + int(np.sum(sizes_x[ib])))
+
+    def apply(self, X, launch=True):
+        res = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
+        if self.empty:
+            return res
+        if X.dtype != self.dtype:
+            X = X.astype(self.dtype)
+        res._set_blocks(self.qdata, arena=dev.empty(self.total, self.dtype), qdata_sorted=True)
+        if not launch:
+            return res
+        dev.check(dev.lib().tpa_mpo_apply_batch(dev.code(self.dtype), self.jobs_dev.data_ptr(), self.n_jobs, self.terms_dev.data_ptr(),
+                                                self.coeff_dev.data_ptr(), self.max_d, self.max_elems, X._arena.data_ptr(),
+                                                res._arena.data_ptr(), dev.stream()), "mpo_apply")
+        return res
+
+    def program_op(self, a_slot, c_slot):
+        """The row of a ``tpa_lanczos_run`` program that applies this plan from slot ``a_slot`` into slot ``c_slot`` (kind 5)."""
+        return [5, 0, self.jobs_dev.data_ptr(), self.terms_dev.data_ptr(), self.coeff_dev.data_ptr(), self.n_jobs, a_slot, self.max_d,
+                c_slot, self.max_elems, 0, 0]
+
 
 def _envs_factorable(LP, RP):
     """LP / RP as the factored forms contract them: the standard labels in an order that needs no transposed copy, MPO bond legs
@@ -374,10 +569,11 @@ def _envs_factorable(LP, RP):
 
 def factored_matvec_possible(LP, RP, W0, W1):
     """Whether ``LP . theta . (W0 W1) . RP`` can run as GEMM / block linear combination / GEMM on the tensors as they are stored:
-    every MPO block a single number, MPO bond legs of the environments resolved into 1-wide blocks, leg orders that need no
-    transposed copy.  ``W0`` / ``W1`` with labels ``p`` or ``p0`` / ``p1``."""
+    every MPO block a single number -- or a small matrix on the physical index between 1-wide MPO bond blocks (``_mpo_plan_class``) --,
+    MPO bond legs of the environments resolved into 1-wide blocks, leg orders that need no transposed copy.  ``W0`` / ``W1`` with
+    labels ``p`` or ``p0`` / ``p1``."""
     w0, w1 = list(W0.get_leg_labels()), list(W1.get_leg_labels())
-    return (_mpo_entries(W0) is not None and _mpo_entries(W1) is not None and _envs_factorable(LP, RP) and
+    return (_envs_factorable(LP, RP) and _mpo_plan_class(W0, W1) is not None and
             w0 in (['wL', 'wR', 'p0', 'p0*'], ['wL', 'wR', 'p', 'p*']) and w1 in (['wL', 'wR', 'p1', 'p1*'], ['wL', 'wR', 'p', 'p*']))
 
 
@@ -458,7 +654,8 @@ class TwoSiteH(_DeviceEffectiveH):
         self.W0 = W0.replace_labels(['p', 'p*'], ['p0', 'p0*'])
         self.W1 = W1.replace_labels(['p', 'p*'], ['p1', 'p1*'])
         # the host copy of the MPO entries is cached on the MPO's own tensors (one D2H read per site for the whole run)
-        self.W0._tpa_entries, self.W1._tpa_entries = _mpo_entries(W0), _mpo_entries(W1)
+        _share_mpo_tables(self.W0, W0)
+        _share_mpo_tables(self.W1, W1)
         self._env = env if tensors is None else None
         self._LHeff = self._RHeff = None
         self._plans = None
@@ -577,8 +774,8 @@ class TwoSiteH(_DeviceEffectiveH):
             p1, l_use, t_use = npc.plan_tensordot(self._LPf, theta, axes=['vR', 'vL'])
             assert l_use is self._LPf and t_use is theta, "factored matvec step 1 must not need a transpose"
             T1 = p1.apply(self._LPf, theta)                                    # vR*, wR, p0, p1, vR
-            a01 = MpoApplyPlan.get(T1, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'p1', 'wR', 'vR'),
-                                   W2=self.W1, x_p2='p1', p2_out='p1', p2_in='p1*')   # both MPO tensors in ONE pass
+            a01 = _mpo_plan_class(self.W0, self.W1).get(T1, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'p1', 'wR', 'vR'),
+                                                        W2=self.W1, x_p2='p1', p2_out='p1', p2_in='p1*')   # both MPO tensors in ONE pass
             T3 = a01.apply(T1)
             p2, t3_use, r_use = npc.plan_tensordot(T3, self._RPf, axes=(['wR', 'vR'], ['wL', 'vL']))
             assert t3_use is T3 and r_use is self._RPf, "factored matvec step 2 must not need a transpose"
@@ -645,8 +842,8 @@ class TwoSiteH(_DeviceEffectiveH):
                 if l_use is not self._LPf or t_use is not theta or p1.empty:
                     return None
                 T1 = p1.apply(self._LPf, theta, launch=False)
-                a01 = MpoApplyPlan.get(T1, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'p1', 'wR', 'vR'),
-                                       W2=self.W1, x_p2='p1', p2_out='p1', p2_in='p1*')
+                a01 = _mpo_plan_class(self.W0, self.W1).get(T1, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'p1', 'wR', 'vR'),
+                                                            W2=self.W1, x_p2='p1', p2_out='p1', p2_in='p1*')
                 if a01.empty:
                     return None
                 T3 = a01.apply(T1, launch=False)
@@ -665,7 +862,7 @@ class TwoSiteH(_DeviceEffectiveH):
                 bufs = [self._LPf._arena, self._RPf._arena, dev.scratch('lanczos_t1', p1.res_total, p1.dtype),
                         dev.scratch('lanczos_t3', a01.total, a01.dtype)]
                 ops = _gemm_ops(p1, 0, -1, 2, bufs, 'lanczos_sk1')
-                ops.append([1, 0, a01.jobs_dev.data_ptr(), a01.terms_dev.data_ptr(), 0, a01.n_jobs, 2, 0, 3, a01.max_elems, 0, 0])
+                ops.append(a01.program_op(2, 3))
                 ops += _gemm_ops(p2, 3, 1, -2, bufs, 'lanczos_sk2')
                 res = (np.array(ops, dtype=np.int64), bufs, (p1, p2))
                 last = p2
@@ -699,7 +896,7 @@ class TwoSiteH(_DeviceEffectiveH):
         if self.factored:       # LP' = A^dagger (LP . A) W0 without LHeff (reference MPOEnvironment._contract_LP, mpo.py:3087)
             A = U.split_legs(['(vL.p0)'])                                        # vL, p0, vR
             X = npc.tensordot(self.LP, A, axes=['vR', 'vL'])                     # vR*, wR, p0, vR
-            X = MpoApplyPlan.get(X, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'wR', 'vR')).apply(X)
+            X = _mpo_plan_class(self.W0).get(X, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'wR', 'vR')).apply(X)
             LP = npc.tensordot(A.conj(), X, axes=(['vL*', 'p0*'], ['vR*', 'p0']))   # vR*, wR, vR
             LP = _relabel_view(LP, list(self.LP.get_leg_labels()))
             _env_set_LP(env, i, LP)
@@ -715,7 +912,7 @@ class TwoSiteH(_DeviceEffectiveH):
         if self.factored:       # RP' = (B . RP) W1 B^dagger without RHeff (reference _contract_RP, mpo.py:3097)
             B = VH.split_legs(['(p1.vR)'])                                       # vL, p1, vR
             X = npc.tensordot(B, self.RP, axes=['vR', 'vL'])                     # vL, p1, wL, vL*
-            X = MpoApplyPlan.get(X, self.W1, 'wL', 'p1', 'wR', 'wL', 'p1', 'p1*', ('vL', 'wL', 'p1', 'vL*')).apply(X)
+            X = _mpo_plan_class(self.W1).get(X, self.W1, 'wL', 'p1', 'wR', 'wL', 'p1', 'p1*', ('vL', 'wL', 'p1', 'vL*')).apply(X)
             RP = npc.tensordot(X, B.conj(), axes=(['p1', 'vL*'], ['p1*', 'vR*']))   # vL, wL, vL*
             RP = _relabel_view(RP, list(self.RP.get_leg_labels()))
             _env_set_RP(env, i, RP)
@@ -743,7 +940,7 @@ class TwoSiteH(_DeviceEffectiveH):
 # ---------------------------------------------------------------------------------------------------------------------
 # One- and zero-site effective Hamiltonians (TDVP: ``one_site_update`` after every two-site update, ``zero_site_update`` after
 # every one-site update of the single-site algorithm), in the factored form of ``TwoSiteH``:
-#     one site   theta [vL, p0, vR]:  T1 = LP . theta (grouped GEMM),  T2 = W0 applied blockwise (MpoApplyPlan),
+#     one site   theta [vL, p0, vR]:  T1 = LP . theta (grouped GEMM),  T2 = W0 applied blockwise (MpoApplyPlan / MpoBlockApplyPlan),
 #                                     theta' = T2 . RP (grouped GEMM chained over wR and the bond sector)
 #     zero sites theta [vL, vR]    :  T1 = LP . theta,  theta' = T1 . RP chained over (wR, vR)
 # instead of three generic tensordots with transposed copies and a K = 1 GEMM per MPO entry (reference mps_common.py:1146-1149,
@@ -758,11 +955,11 @@ class _LocalH(_DeviceEffectiveH):
         self.W0 = None
         if W0 is not None:
             self.W0 = W0.replace_labels(['p', 'p*'], ['p0', 'p0*'])
-            self.W0._tpa_entries = _mpo_entries(W0)      # (host copy of the entries: cached on the MPO's own tensor)
+            _share_mpo_tables(self.W0, W0)               # (host copy of the entries / blocks: cached on the MPO's own tensor)
         self.dtype = dtype
         self._fplans = None
         self.factored = _envs_factorable(LP, RP) and (W0 is None or (
-            _mpo_entries(W0) is not None and list(self.W0.get_leg_labels()) == ['wL', 'wR', 'p0', 'p0*']))
+            list(self.W0.get_leg_labels()) == ['wL', 'wR', 'p0', 'p0*'] and _mpo_plan_class(self.W0) is not None))
         if self.factored:
             self._LPf = _relabel_view(LP, ['vR*', 'wR', 'vR'])
             self._RPf = _relabel_view(RP, ['wL', 'vL', 'vL*'])
@@ -784,7 +981,7 @@ class _LocalH(_DeviceEffectiveH):
         T = p1.apply(self._LPf, theta, launch=False)               # vR*, wR, [p0,] vR
         a0 = None
         if self.W0 is not None:
-            a0 = MpoApplyPlan.get(T, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'wR', 'vR'))
+            a0 = _mpo_plan_class(self.W0).get(T, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'wR', 'vR'))
             if a0.empty:
                 return None
             T = a0.apply(T, launch=False)                          # vR*, p0, wR, vR
@@ -805,7 +1002,7 @@ class _LocalH(_DeviceEffectiveH):
             if fp['a0'] is not None:
                 T = fp['a0'].apply(T)
             res = fp['p2'].apply(T, self._RPf)
-        else:               # the reference's contractions (MPO blocks that are not single numbers, no charges, empty theta)
+        else:               # the reference's contractions (MPO bond legs with wider blocks, no charges, empty theta)
             res = npc.tensordot(self.LP, theta, axes=['vR', 'vL'])
             if self.W0 is not None:
                 res = npc.tensordot(self.W0, res, axes=[['wL', 'p0*'], ['wR', 'p0']])
@@ -834,7 +1031,7 @@ class _LocalH(_DeviceEffectiveH):
                 if a0 is not None:
                     bufs.append(dev.scratch('lanczos_t3', a0.total, a0.dtype))
                     src = len(bufs) - 1
-                    ops.append([1, 0, a0.jobs_dev.data_ptr(), a0.terms_dev.data_ptr(), 0, a0.n_jobs, 2, 0, src, a0.max_elems, 0, 0])
+                    ops.append(a0.program_op(2, src))
                 ops += _gemm_ops(p2, src, 1, -2, bufs, 'lanczos_sk2')
                 res, last = (np.array(ops, dtype=np.int64), bufs, (p1, p2)), p2
         return self._file_program(theta, res, last)

@@ -125,7 +125,10 @@ def restrict_plan_rows(plan, res_leg0, lo, hi):
 
 
 class ShardedTwoSiteH(TwoSiteH):
-    """TwoSiteH whose matvec is sharded over ``torch.distributed`` ranks by rows of theta'."""
+    """TwoSiteH whose matvec is sharded over ``torch.distributed`` ranks by rows of theta'.
+
+    The factored form is sharded for MPOs whose blocks are single numbers only: the row-restricted tables below are those of
+    ``MpoApplyPlan``.  MPOs with small matrices as blocks (``MpoBlockApplyPlan``) keep the row panels of LHeff."""
 
     def __init__(self, env, i0, combine=True, move_right=True, group=None):
         super().__init__(env, i0, combine, move_right)      # factored when the MPO allows it, else row panels of LHeff
@@ -134,6 +137,10 @@ class ShardedTwoSiteH(TwoSiteH):
         self.world = d.get_world_size(group)
         self.rank = d.get_rank(group)
         self._sharded = None
+
+    def _factored_possible(self):
+        from .mps_common import _mpo_entries
+        return _mpo_entries(self.W0) is not None and _mpo_entries(self.W1) is not None and super()._factored_possible()
 
     def _build_sharded(self, theta):
         p1, _, _ = npc.plan_tensordot(self.LHeff, theta, axes=['(vR.p0*)', '(vL.p0)'])

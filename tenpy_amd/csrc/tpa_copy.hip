@@ -82,6 +82,105 @@ __global__ __launch_bounds__(NT) void lincomb_kernel(const LinJob *__restrict__ 
     }
 }
 
+// ---- dst slab (pre, d_out, post) = sum_t M_t (d_out x d_in_t) applied on the middle index of src_t slab (pre, d_in_t, post) --------
+// What it replaces: the W0 / W1 tensordots of TwoSiteH.matvec (reference mps_common.py:1321-1348) and the W0 tensordot of
+// OneSiteH.matvec (:1146-1149) for MPO tensors whose bond legs have 1-wide blocks while a physical charge sector holds several
+// states (spinful fermions with N only, spin-1 / bosons with parity, grouped sites): the MPO step of the factored matvec is then
+// small dense matrices on the physical index instead of the single numbers of lincomb_kernel.  HBM-bound: every source element is
+// read once per term, every destination element is written once.
+// Launch geometry (tests/test_conformance_mpo_apply.py repeats it):
+//   item     = 16 bytes in the VEC form (one complex element, or two real elements j, j + 1 of one row) -- 16-byte loads and stores;
+//              the scalar form (8-byte accesses, item = one element) serves base addresses off a 16-byte boundary and, for real data,
+//              jobs with an odd post, dst_off or src_off (decided per job, uniform over the workgroup).
+//   thread   = one column (i, item of j): d_out accumulators in registers (D = 2, 4, 8 or 16 of them: the smallest that holds the
+//              max_d of the call), one read of its d_in items per term, terms in table order, c ascending, one chain of fused
+//              multiply-adds per component.  j is the fastest index: loads and stores of a wavefront are contiguous.
+//   coeff    : the address does not depend on the lane -- uniform (scalar) loads, no LDS.
+//   grid     = (min(512, ceil(max_job_elems / (max_d NT))), n_jobs), grid-stride over the columns of the job.
+struct MpoJob {   // int64[8]
+    int64_t dst_off, pre, d_out, post, term_begin, term_count, pad0, pad1;
+};
+struct MpoTerm {  // int64[4]
+    int64_t src_off, d_in, coeff_off, pad;
+};
+
+template <bool CPLX, int D, bool VEC>
+__device__ __forceinline__ void mpo_apply_job(const MpoJob &J, const MpoTerm *__restrict__ T, const double *__restrict__ coeff,
+                                              const double *__restrict__ src, double *__restrict__ dst) {
+    constexpr int W = (CPLX || VEC) ? 2 : 1;           // doubles per item
+    constexpr int EPI = (!CPLX && VEC) ? 2 : 1;        // elements per item
+    constexpr int CW = CPLX ? 2 : 1;                   // doubles per coefficient
+    const int d_out = (int)J.d_out, nt = (int)J.term_count;
+    const int64_t post_items = J.post / EPI;
+    const int64_t n_cols = J.pre * post_items;
+    const int64_t row_d = post_items * W;              // doubles from (i, o, j) to (i, o + 1, j)
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n_cols; e += (int64_t)gridDim.x * NT) {
+        const int64_t i = e / post_items, jj = e - i * post_items;
+        double2 acc[D];
+#pragma unroll
+        for (int o = 0; o < D; ++o) acc[o] = double2{0., 0.};
+        for (int t = 0; t < nt; ++t) {
+            const int d_in = (int)T[t].d_in;
+            const double *x = src + CW * T[t].src_off + (i * d_in * post_items + jj) * W;
+            const double *m = coeff + CW * T[t].coeff_off;
+            for (int c = 0; c < d_in; ++c) {
+                double2 v;
+                if (VEC) {
+                    v = *reinterpret_cast<const double2 *>(x + c * row_d);
+                } else {
+                    v.x = x[c * row_d];
+                    v.y = CPLX ? x[c * row_d + 1] : 0.;
+                }
+#pragma unroll
+                for (int o = 0; o < D; ++o) {
+                    if (o < d_out) {
+                        const double *a = m + CW * (o * d_in + c);
+                        if (CPLX) {
+                            acc[o].x = fma(a[0], v.x, acc[o].x);
+                            acc[o].x = fma(-a[1], v.y, acc[o].x);
+                            acc[o].y = fma(a[0], v.y, acc[o].y);
+                            acc[o].y = fma(a[1], v.x, acc[o].y);
+                        } else {
+                            acc[o].x = fma(a[0], v.x, acc[o].x);
+                            if (VEC) acc[o].y = fma(a[0], v.y, acc[o].y);
+                        }
+                    }
+                }
+            }
+        }
+        double *y = dst + CW * J.dst_off + (i * d_out * post_items + jj) * W;
+#pragma unroll
+        for (int o = 0; o < D; ++o) {
+            if (o < d_out) {
+                if (VEC) {
+                    *reinterpret_cast<double2 *>(y + o * row_d) = acc[o];
+                } else {
+                    y[o * row_d] = acc[o].x;
+                    if (CPLX) y[o * row_d + 1] = acc[o].y;
+                }
+            }
+        }
+    }
+}
+
+template <bool CPLX, int D, bool VEC>
+__global__ __launch_bounds__(NT) void mpo_apply_kernel(const MpoJob *__restrict__ jobs, const MpoTerm *__restrict__ terms,
+                                                       const double *__restrict__ coeff, const double *__restrict__ src,
+                                                       double *__restrict__ dst) {
+    const MpoJob J = jobs[blockIdx.y];
+    const MpoTerm *T = terms + J.term_begin;
+    if (J.pre <= 0 || J.d_out <= 0 || J.post <= 0) return;
+    if (VEC && !CPLX) {         // two real elements per item: the whole job has to keep the items on 16-byte boundaries
+        bool even = ((J.post | J.dst_off) & 1) == 0;
+        for (int t = 0; t < (int)J.term_count; ++t) even = even && (T[t].src_off & 1) == 0;
+        if (!even) {
+            mpo_apply_job<CPLX, D, false>(J, T, coeff, src, dst);
+            return;
+        }
+    }
+    mpo_apply_job<CPLX, D, VEC>(J, T, coeff, src, dst);
+}
+
 struct ScaleJob {  // int64[6]
     int64_t x_off, pre, len, post, s_off, pad;
 };
@@ -220,6 +319,51 @@ extern "C" int tpa_lincomb_batch(int dtype, const int64_t *jobs_dev, int n_jobs,
         lincomb_kernel<false><<<grid, NT, 0, st>>>((const LinJob *)jobs_dev, (const LinTerm *)terms_dev, (const double *)src_base, (double *)dst_base);
     else
         lincomb_kernel<true><<<grid, NT, 0, st>>>((const LinJob *)jobs_dev, (const LinTerm *)terms_dev, (const double *)src_base, (double *)dst_base);
+    TPA_LAUNCH_CHECK();
+    return 0;
+}
+
+template <bool CPLX, bool VEC>
+static void mpo_apply_launch(int max_d, dim3 grid, hipStream_t st, const int64_t *jobs_dev, const int64_t *terms_dev, const void *coeff_dev,
+                             const void *src_base, void *dst_base) {
+    const MpoJob *jobs = (const MpoJob *)jobs_dev;
+    const MpoTerm *terms = (const MpoTerm *)terms_dev;
+    const double *coeff = (const double *)coeff_dev, *src = (const double *)src_base;
+    double *dst = (double *)dst_base;
+    if (max_d <= 2)
+        mpo_apply_kernel<CPLX, 2, VEC><<<grid, NT, 0, st>>>(jobs, terms, coeff, src, dst);
+    else if (max_d <= 4)
+        mpo_apply_kernel<CPLX, 4, VEC><<<grid, NT, 0, st>>>(jobs, terms, coeff, src, dst);
+    else if (max_d <= 8)
+        mpo_apply_kernel<CPLX, 8, VEC><<<grid, NT, 0, st>>>(jobs, terms, coeff, src, dst);
+    else
+        mpo_apply_kernel<CPLX, 16, VEC><<<grid, NT, 0, st>>>(jobs, terms, coeff, src, dst);
+}
+
+extern "C" int tpa_mpo_apply_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const int64_t *terms_dev, const void *coeff_dev,
+                                   int max_d, int64_t max_job_elems, const void *src_base, void *dst_base, void *stream) {
+    static_assert(TPA_MPO_APPLY_MAXD == 16, "mpo_apply_launch dispatches up to 16 accumulators");
+    TPA_ARG_CHECK(dtype == TPA_F64 || dtype == TPA_C128);
+    TPA_ARG_CHECK(max_d >= 1 && max_d <= TPA_MPO_APPLY_MAXD);
+    if (n_jobs <= 0) return 0;
+    TPA_ARG_CHECK(n_jobs <= 65535);
+    int64_t g = (max_job_elems / max_d + NT - 1) / NT;
+    if (g < 1) g = 1;
+    if (g > 512) g = 512;
+    dim3 grid((int)g, n_jobs);
+    hipStream_t st = (hipStream_t)stream;
+    const bool aligned = (((uintptr_t)src_base | (uintptr_t)dst_base) & 15) == 0;
+    if (dtype == TPA_F64) {
+        if (aligned)
+            mpo_apply_launch<false, true>(max_d, grid, st, jobs_dev, terms_dev, coeff_dev, src_base, dst_base);
+        else
+            mpo_apply_launch<false, false>(max_d, grid, st, jobs_dev, terms_dev, coeff_dev, src_base, dst_base);
+    } else {
+        if (aligned)
+            mpo_apply_launch<true, true>(max_d, grid, st, jobs_dev, terms_dev, coeff_dev, src_base, dst_base);
+        else
+            mpo_apply_launch<true, false>(max_d, grid, st, jobs_dev, terms_dev, coeff_dev, src_base, dst_base);
+    }
     TPA_LAUNCH_CHECK();
     return 0;
 }

@@ -771,6 +771,11 @@ extern "C" int tpa_lanczos_run_ex(int dtype, int64_t n, const int64_t *ops, int 
                 TPA_ARG_CHECK(a != nullptr && b != nullptr && c != nullptr && op[2] != 0 && op[5] >= 0 && op[5] <= PJ_MAX);
                 double *pw = (double *)op[2];
                 if (int rc = tpa_project_out(dtype, n, a, (int)op[5], op[3], b, c, pw, nullptr, pw + 2 * op[5] + 2, stream)) return rc;
+            } else if (op[0] == 5) {        // MPO step with small dense matrices on the physical index (op[7] holds max_d, not a slot)
+                TPA_ARG_CHECK(a != nullptr && c != nullptr);
+                if (int rc = tpa_mpo_apply_batch(dtype, (const int64_t *)op[2], (int)op[5], (const int64_t *)op[3], (const void *)op[4],
+                                                 (int)op[7], op[9], a, c, stream))
+                    return rc;
             } else {
                 TPA_ARG_CHECK(false && "unknown op kind");
             }

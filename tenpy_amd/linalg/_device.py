@@ -28,6 +28,16 @@ def lib():
     return _lib.load()
 
 
+def lib_provides(name):
+    """Whether the installed library object really implements the entry point ``name``: the ctypes handle when the symbol exists, any
+    other object (an emulation that forwards names it does not know to the real library, which would then be handed host pointers)
+    only when it defines the name itself.  Callers take their older route where this says no; the call is never forwarded."""
+    L = lib()
+    if isinstance(L, ctypes.CDLL):
+        return hasattr(L, name)
+    return name in vars(L) or any(name in vars(k) for k in type(L).__mro__)
+
+
 _raw_stream = None
 
 

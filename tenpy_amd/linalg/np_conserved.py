@@ -1651,6 +1651,7 @@ def clear_device_caches():
         from ..algorithms import mps_common as _mc
         _mc._heff_plans.clear()
         _mc.MpoApplyPlan._cache.clear()
+        _mc.MpoBlockApplyPlan._cache.clear()
     except ImportError:      # (the linalg package is importable on its own)
         pass
 

@@ -35,17 +35,25 @@ def hubbard_ops():
     return ops
 
 
-def spinful_fermion_leg():
-    """Physical leg with charges (N, 2Sz) for (empty, up, down, full)."""
-    chinfo = ChargeInfo([1, 1], ['N', '2*Sz'])
-    leg = LegCharge.from_qflat(chinfo, [[0, 0], [1, 1], [1, -1], [2, 0]])
-    return chinfo, leg
+def spinful_fermion_leg(conserve=('N', '2*Sz')):
+    """Physical leg for (empty, up, down, full) with the charges named in ``conserve``: (N, 2Sz) by default; ``('N',)`` gives the
+    sectors N = 0, 1, 2 of widths 1, 2, 1 (up and down share one charge block, as a sorted and bunched site leg has them)."""
+    conserve = tuple(conserve)
+    if conserve == ('N', '2*Sz'):
+        chinfo = ChargeInfo([1, 1], ['N', '2*Sz'])
+        return chinfo, LegCharge.from_qflat(chinfo, [[0, 0], [1, 1], [1, -1], [2, 0]])
+    if conserve == ('N',):
+        chinfo = ChargeInfo([1], ['N'])
+        return chinfo, LegCharge.from_qind(chinfo, [0, 1, 3, 4], [[0], [1], [2]])
+    raise ValueError("conserve must be ('N', '2*Sz') or ('N',), got %r" % (conserve,))
 
 
-def hubbard_ladder_mpo(Lx, t=1., U=8., mu=0., Ly=2):
-    """MPO of the Ly=2 ladder of length Lx (2 Lx chain sites), D = 10."""
+def hubbard_ladder_mpo(Lx, t=1., U=8., mu=0., Ly=2, conserve=('N', '2*Sz'), peierls=0.):
+    """MPO of the Ly=2 ladder of length Lx (2 Lx chain sites), D = 10.  ``conserve``: see ``spinful_fermion_leg``.  ``peierls``: the
+    hoppings along leg y = 0 get the phase exp(+i peierls), those along y = 1 exp(-i peierls) (a flux of 2 peierls per plaquette;
+    the MPO is complex when it is not zero)."""
     assert Ly == 2
-    chinfo, p = spinful_fermion_leg()
+    chinfo, p = spinful_fermion_leg(conserve)
     o = hubbard_ops()
     N = 2 * Lx
     JW = o['JW']
@@ -55,7 +63,7 @@ def hubbard_ladder_mpo(Lx, t=1., U=8., mu=0., Ly=2):
     D = 10          # 0: IdL, 1-4: term k waiting for its partner, 5-8: term k after one JW site, 9: IdR
     Ws = []
     for s in range(N):
-        W = np.zeros((D, D, 4, 4))
+        W = np.zeros((D, D, 4, 4), dtype=np.complex128 if peierls else np.float64)
         W[0, 0] = o['Id']
         W[9, 9] = o['Id']
         W[0, 9] = U * o['NuNd'] - mu * o['Ntot']
@@ -64,12 +72,15 @@ def hubbard_ladder_mpo(Lx, t=1., U=8., mu=0., Ly=2):
             W[1 + k, 5 + k] = JW
             if s % 2 == 1:                      # rung: partner of the operator placed on site s-1 (even)
                 W[1 + k, 9] = -t * second[k]
-            W[5 + k, 9] = -t * second[k]        # leg: partner of the operator placed on site s-2
+            leg_t = t
+            if peierls:                         # c^dag_i c_j (k even) with the phase of its leg, the h.c. term (k odd) with the conjugate
+                leg_t = t * np.exp(1j * peierls * (1 - 2 * (s % 2)) * (1 - 2 * (k % 2)))
+            W[5 + k, 9] = -leg_t * second[k]    # leg: partner of the operator placed on site s-2
         Ws.append(W)
     # an operator placed on an odd site must not find a rung partner on the next (even) site: handled above
     # (rung entry only on odd s).  Open boundaries: first / last tensors are the IdL row / IdR column.
     Ws[0] = Ws[0][0:1]
     Ws[-1] = Ws[-1][:, 9:10]
-    H = mpo_from_dense(Ws, [p] * N, chinfo)
+    H = mpo_from_dense(Ws, [p] * N, chinfo, dtype=Ws[0].dtype)
     H.IdL, H.IdR = 0, -1
     return H
