@@ -142,6 +142,9 @@ int tpa_project_out(int dtype, int64_t n, const void *basis_dev, int m, int64_t 
  *         kind 5: {5, 0, jobs, terms, coeff, n_jobs, a_slot, max_d, c_slot, max_elems, 0, 0} -- tpa_mpo_apply_batch(dtype, jobs = p0,
  *                 n_jobs = count, terms = p1, coeff = p2, max_d (in the place of b_slot), max_elems, src = A, dst = C): the MPO step of
  *                 a factored operator whose MPO blocks are small matrices.  Not counted as GEMM time.
+ *         kind 6: {6, 0, jobs, rows, terms, n_jobs, a_slot, 0, c_slot, max_cols, 0, 0} -- tpa_mpo_entry_apply_batch(dtype, jobs = p0,
+ *                 n_jobs = count, rows = p1, terms = p2, max_job_cols = max_elems, src = A, dst = C): the MPO step of a factored operator
+ *                 whose MPO index sits inside the blocks (wide MPO bond blocks, wide sectors).  Not counted as GEMM time.
  *         slots: >= 0 -> bufs[slot] (HOST array of n_bufs device pointers: fixed operands and temporaries), -1 -> the input
  *         vector v_k, -2 -> the output vector w of this matvec.  (p0..p2 are device pointers stored as integers.)
  *   krylov_dev : (N_max + 1) * n elements; on return vectors 0 .. N-1 are the orthonormal Krylov basis (v_0 = psi0 / |psi0|).
@@ -223,6 +226,26 @@ int tpa_lincomb_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const int6
 #define TPA_MPO_APPLY_MAXD 16
 int tpa_mpo_apply_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const int64_t *terms_dev, const void *coeff_dev, int max_d,
                         int64_t max_job_elems, const void *src_base, void *dst_base, void *stream);
+/* dst slab (pre, n_rows, post): row o = sum_t alpha_t * (one middle row of a src slab), batched, one job per destination slab: the MPO
+ * step of the factored effective Hamiltonians entry by entry, for the MPO tensors tpa_lincomb_batch and tpa_mpo_apply_batch do not
+ * serve -- MPO bond legs with blocks wider than 1 (sorted bond legs), physical sectors wider than TPA_MPO_APPLY_MAXD, no conserved
+ * charge.  A single entry of W (two sites: of sum_w'' W0[w, w''] W1[w'', w']) takes one middle row c of a block (pre, M_in, post) of the
+ * source to one middle row o of a block (pre, M_out, post) of the destination.
+ * jobs : int64[n_jobs][8] = {dst_off, pre, n_rows, post, row_begin, dst_ld, 0, 0}     dst_ld = 0 means n_rows * post
+ * rows : int64[..][2]     = {term_begin, term_count}                                  row o of a job: rows[row_begin + o], o < n_rows
+ * terms: int64[..][4]     = {src_off, src_ld, alpha_re, alpha_im}                     the terms of tpa_lincomb_batch (bit patterns)
+ *   dst[dst_off + i*dst_ld + o*post + j] = sum_t alpha_t * src[src_off_t + i*src_ld_t + j]      for i < pre, o < n_rows, j < post
+ * Offsets and strides in elements of dtype; src_off already contains c * post.  dst_ld > n_rows * post lets several jobs share one
+ * block (each a range of its rows).  max_job_cols = max pre * post over the jobs sizes the grid, capped at 512 workgroups per job
+ * (larger jobs loop).  One job per blockIdx.y like the other batched entry points of this section: dtype is checked first, then
+ * n_jobs <= 0 returns 0 without a launch and n_jobs > 65535 returns TPA_E_BADARG; all argument errors before anything is launched; jobs
+ * with a zero extent do nothing.  Every element of a destination slab is written exactly once -- a row with term_count = 0 writes zeros
+ * --, nothing else is written; src and dst must not overlap.  Summation order: the terms of a row in table order, one chain of fused
+ * multiply-adds per component (real: term_count, complex: twice that) -- two identical calls give identical bits.
+ * Traffic: itemsize (sum_terms pre post + sum_jobs pre n_rows post) bytes.  16-byte loads and stores where src_base and dst_base are
+ * 16-byte aligned and, for F64, post, dst_off, dst_ld and every src_off and src_ld of the job are even; 8-byte ones otherwise. */
+int tpa_mpo_entry_apply_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const int64_t *rows_dev, const int64_t *terms_dev,
+                              int64_t max_job_cols, const void *src_base, void *dst_base, void *stream);
 /* x_b[i, j, l] *= s[s_off_b + j]  for each block b viewed as (pre, len, post).  Replaces
  * iscale_axis, np_conserved.py:2132-2140.  jobs: int64[n][6] = {x_off, pre, len, post, s_off, 0};
  * the scale vector s is real (F64) or of `dtype` when s_is_complex. */

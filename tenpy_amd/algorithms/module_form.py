@@ -8,11 +8,12 @@
   ``tenpy_amd.algorithms.mps_common.TwoSiteH``: cached contraction plans, fused ``LHeff`` build, and -- for
   ``combine=False``, the reference's default -- the factored matvec ``LP . theta . (W0 W1) . RP`` with the MPO tensors
   applied blockwise -- linear combinations of blocks where every MPO block is a single number, small dense matrices on the
-  physical index where a charge sector of the site holds several states (``mps_common.MpoBlockApplyPlan``) -- instead of K = 1
-  GEMMs.  Bonds the device form does not cover (sectors below ``MIN_SECTOR``, MPOs without a conserved charge, MPO bond legs with blocks wider than 1
-  -- MPOs after ``sort_legcharges`` --, physical sectors wider than ``TPA_MPO_APPLY_MAXD`` (two sites: their product),
-  ``H + h.c.`` environments, exact diagonalisation of small bonds) get the reference's own class: ``__new__`` dispatches, so the
-  engines see one ``EffectiveH``.
+  physical index where a charge sector of the site holds several states (``mps_common.MpoBlockApplyPlan``), single entries between
+  the middle rows of blocks where MPO bond legs have blocks wider than 1 -- MPOs after ``sort_legcharges`` -- or physical sectors are
+  wider than ``TPA_MPO_APPLY_MAXD`` (two sites: their product) (``mps_common.MpoEntryApplyPlan``) -- instead of K = 1
+  GEMMs.  Bonds the device form does not cover (sectors below ``MIN_SECTOR``, MPOs without a conserved charge unless
+  ``TPA_MPO_ENTRY_APPLY=2``, ``H + h.c.`` environments, exact diagonalisation of small bonds) get the reference's own class:
+  ``__new__`` dispatches, so the engines see one ``EffectiveH``.
 * ``device_one_site_h(RefOneSiteH)`` / ``device_zero_site_h(RefZeroSiteH)`` -> the same for the operators TDVP constructs after
   every two-site / one-site update (``tdvp.py:308 one_site_update``, ``:419 zero_site_update``) on top of
   ``mps_common.OneSiteH`` / ``ZeroSiteH``; ``combine=True``, ``H + h.c.`` environments, MPO tensors without a blockwise form
@@ -151,7 +152,7 @@ def device_one_site_h(Ref):
             if combine or not _plain_env(env):
                 return None
             LP, W0, RP = env.get_LP(i0), env.H.get_W(i0), env.get_RP(i0)
-            if list(W0.get_leg_labels()) != ['wL', 'wR', 'p', 'p*'] or not dev_mc._envs_factorable(LP, RP) or dev_mc._mpo_plan_class(W0) is None:
+            if list(W0.get_leg_labels()) != ['wL', 'wR', 'p', 'p*'] or dev_mc._factored_plan_class(LP, RP, W0) is None:
                 return None
             return LP, W0, RP
 

@@ -12,7 +12,8 @@ MI355X-first differences:
 * both contraction plans are built once per bond and replayed for every Lanczos step: one matvec is
   exactly two grouped-GEMM launches, no host planning, no allocation besides the result arena;
 * ``factored`` mode (default when every block of W0, W1 is a single number, or a small matrix on the physical index between 1-wide
-  blocks of the MPO bond legs -- sites with several states per charge sector): the same operator applied as
+  blocks of the MPO bond legs -- sites with several states per charge sector --, or, entry by entry, any block structure of a
+  charged MPO: sorted and bunched MPO bond legs, wide sectors, ``MpoEntryApplyPlan``): the same operator applied as
   ``LP . theta . (W0 W1) . RP`` -- two GEMM launches with a factor d fewer flops (the physical legs are not fused into
   the contracted index) plus one block-level linear combination for the two MPO tensors; LHeff / RHeff are then only
   built on demand (mixer, tests).  theta stays in its un-fused form (vL, p0, p1, vR) during the Lanczos iteration and
@@ -37,6 +38,12 @@ FACTORED_MIN_SECTOR = 200
 # small dense matrices on the physical index (``MpoBlockApplyPlan``, tpa_mpo_apply_batch).  A/B knob: '0' = the routing without it.
 BLOCK_APPLY = _os.environ.get('TPA_MPO_BLOCK_APPLY', '1') != '0'
 from .._lib import MPO_APPLY_MAXD      # noqa: E402  (TPA_MPO_APPLY_MAXD)
+# MPO tensors neither of the two plans above serves -- MPO bond legs with blocks wider than 1 (sorted and bunched bond legs), physical
+# sectors wider than ``TPA_MPO_APPLY_MAXD`` (two sites: their product): the MPO step entry by entry (``MpoEntryApplyPlan``,
+# tpa_mpo_entry_apply_batch).  0 = the routing without it, 1 = MPOs with a conserved charge, 2 = also MPOs without one.  2 is not the
+# default: tests/test_onesite_heff.py::test_generic_route_without_charges states the reference's contractions as the route of a
+# charge-free MPO on both backends, and nothing has been measured that would justify moving it.
+ENTRY_APPLY = int(_os.environ.get('TPA_MPO_ENTRY_APPLY', '1'))
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Fused construction of LHeff / RHeff:  LP.W0 (resp. W1.RP) + combine_legs in ONE kernel launch.
@@ -374,8 +381,9 @@ class MpoApplyPlan:
 
 def _mpo_blocks(W):
     """(qdata, host copies of the stored blocks) of an MPO tensor whose two MPO bond legs have 1-wide blocks and whose physical charge
-    sectors are at most ``TPA_MPO_APPLY_MAXD`` wide, else ``None`` (cached on W like ``_tpa_entries``).  MPOs without a conserved
-    charge are out of scope whatever the blocking of their legs (no charge rule to select the terms: the reference's contractions)."""
+    sectors are at most ``TPA_MPO_APPLY_MAXD`` wide, else ``None`` (cached on W like ``_tpa_entries``).  Wider bond blocks or sectors
+    go entry by entry (``_mpo_coo`` / ``MpoEntryApplyPlan``), and so do MPOs without a conserved charge -- one dense block, no charge
+    rule to select the terms -- where ``ENTRY_APPLY`` is 2; by default they keep the reference's contractions."""
     blk = getattr(W, '_tpa_blocks', False)
     if blk is False:
         labels = list(W.get_leg_labels())
@@ -394,6 +402,47 @@ def _share_mpo_tables(W_new, W):
     W_new._tpa_entries = _mpo_entries(W)
     if W_new._tpa_entries is None and BLOCK_APPLY and dev.lib_provides('tpa_mpo_apply_batch'):
         W_new._tpa_blocks = _mpo_blocks(W)
+    W_new._tpa_origin = W       # (``_mpo_coo`` reads and caches its table there when a plan first asks for it)
+
+
+def _mpo_coo(W):
+    """(global indices int64[n, 4] in the stored leg order, values) of the nonzero entries of an MPO tensor with legs ``wL``, ``wR``
+    and two physical legs, whatever the widths of its blocks; ``None`` for anything else (cached on W like ``_tpa_entries``)."""
+    coo = getattr(W, '_tpa_coo', False)
+    if coo is False and getattr(W, '_tpa_origin', None) is not None:      # a relabelled copy: the table of the MPO's own tensor
+        coo = W._tpa_coo = _mpo_coo(W._tpa_origin)
+    if coo is False:
+        labels = list(W.get_leg_labels())
+        coo = None
+        if W.rank == 4 and 'wL' in labels and 'wR' in labels and W.stored_blocks > 0:
+            idx, vals = [], []
+            for q, b in zip(np.array(W._qdata).tolist(), W._data):
+                b = np.array(b)
+                nz = np.nonzero(b)
+                idx.append(np.stack([nz[a] + int(W.legs[a].slices[q[a]]) for a in range(4)], axis=1))
+                vals.append(b[nz])
+            coo = (np.concatenate(idx).astype(np.int64).reshape(-1, 4), np.concatenate(vals))
+        W._tpa_coo = coo
+    return coo
+
+
+def _entry_route(chinfo):
+    """Whether the entry-by-entry MPO step may serve tensors of this charge structure (switches and the installed library)."""
+    return (ENTRY_APPLY > 0 and BLOCK_APPLY and (chinfo.qnumber > 0 or ENTRY_APPLY == 2) and
+            dev.lib_provides('tpa_mpo_entry_apply_batch'))
+
+
+_STANDARD_W_LABELS = (['wL', 'wR', 'p', 'p*'], ['wL', 'wR', 'p0', 'p0*'], ['wL', 'wR', 'p1', 'p1*'])
+
+
+def _mpo_entry_plan_class(W, W2=None):
+    """``MpoEntryApplyPlan`` where it may serve ``W`` (and ``W2``), else ``None``: asked only where the two older plans decline."""
+    if not _entry_route(W.chinfo):
+        return None
+    for T in (W,) if W2 is None else (W, W2):
+        if list(T.get_leg_labels()) not in _STANDARD_W_LABELS or _mpo_coo(T) is None:
+            return None
+    return MpoEntryApplyPlan
 
 
 def _phys_width(W):
@@ -404,15 +453,19 @@ def _mpo_plan_class(W, W2=None):
     """The plan class that applies the MPO tensor ``W`` (with ``W2``: both neighbours in one pass) to the blocks of a tensor:
     ``MpoApplyPlan`` when every stored block is a single number, ``MpoBlockApplyPlan`` when the MPO bond legs have 1-wide blocks and
     the physical sectors (two sites: their products) are at most ``TPA_MPO_APPLY_MAXD`` wide and the installed library provides
-    ``tpa_mpo_apply_batch``; ``None`` when there is no blockwise form."""
+    ``tpa_mpo_apply_batch``; ``MpoEntryApplyPlan`` where both decline and the tensors carry the standard labels, the MPO has a
+    conserved charge (or ``ENTRY_APPLY`` is 2) and the library provides ``tpa_mpo_entry_apply_batch``; ``None`` when there is no
+    blockwise form.  ``BLOCK_APPLY`` off restores the routing before both of the younger plans."""
     if _mpo_entries(W) is not None and (W2 is None or _mpo_entries(W2) is not None):
         return MpoApplyPlan
-    if not BLOCK_APPLY or not dev.lib_provides('tpa_mpo_apply_batch'):
+    if not BLOCK_APPLY:
         return None
+    if not dev.lib_provides('tpa_mpo_apply_batch'):
+        return _mpo_entry_plan_class(W, W2)
     if _mpo_blocks(W) is None or (W2 is not None and _mpo_blocks(W2) is None):
-        return None
+        return _mpo_entry_plan_class(W, W2)
     if _phys_width(W) * (1 if W2 is None else _phys_width(W2)) > MPO_APPLY_MAXD:
-        return None
+        return _mpo_entry_plan_class(W, W2)
     return MpoBlockApplyPlan
 
 
@@ -558,13 +611,208 @@ class MpoBlockApplyPlan:
                 c_slot, self.max_elems, 0, 0]
 
 
+def _leg_block_pos(leg, idx):
+    """(block number, position inside the block) of the global indices ``idx`` of ``leg``."""
+    sl = np.asarray(leg.slices, dtype=np.int64)
+    b = np.searchsorted(sl, idx, side='right') - 1
+    return b, idx - sl[b]
+
+
+class MpoEntryApplyPlan:
+    """``MpoApplyPlan`` for MPO tensors of any block structure -- MPO bond legs with blocks wider than 1, physical sectors wider than
+    ``TPA_MPO_APPLY_MAXD``, no conserved charge -- entry by entry.  X has its two virtual legs first and last and the MPO and physical
+    legs between them, so a block of X is ``(pre, M_in, post)`` in memory and the block of Y it feeds is ``(pre, M_out, post)`` with the
+    middle legs in the order of ``out_labels``: a single entry of W (two sites: of ``sum_w'' W[w, w''] W2[w'', w']``, joined once on the
+    host, exact zeros dropped) takes one middle row of a block of X to one middle row of a block of Y; the global indices map to
+    (block, position inside the block) through the leg slices.  One ``tpa_mpo_entry_apply_batch`` launch with one job per block of Y,
+    or -- calls with few blocks -- per range of its rows.  Arguments and attributes: see ``MpoApplyPlan``."""
+    _cache = {}
+    SPLIT_BELOW = 512       # calls with fewer blocks of Y than this split the rows of a block over several jobs
+
+    @classmethod
+    def get(cls, X, W, *args, W2=None, **kwargs):
+        """Cached constructor: the plan depends on the block structure of X and on the MPO tensors only."""
+        c1, c2 = _mpo_coo(W), (None if W2 is None else _mpo_coo(W2))
+        key = (X._struct_key(), str(X.dtype), id(c1), None if c2 is None else id(c2), args,
+               tuple(sorted(kwargs.items())), tuple(X.get_leg_labels()))
+        plan = cls._cache.get(key)
+        if plan is None or plan._coo_alive[0] is not c1 or plan._coo_alive[1] is not c2:
+            if len(cls._cache) > 4096:
+                cls._cache.clear()
+            plan = cls._cache[key] = cls(X, W, *args, W2=W2, **kwargs)
+            plan._coo_alive = (c1, c2)          # the key holds id()s: see MpoApplyPlan.get
+        return plan
+
+    @staticmethod
+    def _entries(W, w_in, w_out, p_out, p_in):
+        """Global indices (w_in, w_out, p_out, p_in) and values of the nonzero entries of ``W``."""
+        idx, vals = _mpo_coo(W)
+        wl = list(W.get_leg_labels())
+        return idx[:, [wl.index(w_in), wl.index(w_out), wl.index(p_out), wl.index(p_in)]], vals
+
+    def __init__(self, X, W, x_w, x_p, w_in, w_out, p_out, p_in, out_labels, W2=None, x_p2=None, p2_out=None, p2_in=None):
+        keys, vals = self._entries(W, w_in, w_out, p_out, p_in)
+        if W2 is not None:              # join over the common MPO bond; equal keys are summed in a fixed order
+            keys2, vals2 = self._entries(W2, w_in, w_out, p2_out, p2_in)
+            o2 = np.argsort(keys2[:, 0], kind='stable')
+            lo, hi = np.searchsorted(keys2[o2, 0], keys[:, 1], side='left'), np.searchsorted(keys2[o2, 0], keys[:, 1], side='right')
+            i1 = np.repeat(np.arange(len(keys)), hi - lo)
+            i2 = o2[np.arange(len(i1)) - np.repeat(np.cumsum(hi - lo) - (hi - lo), hi - lo) + np.repeat(lo, hi - lo)]
+            joined = np.stack([keys[i1, 0], keys2[i2, 1], keys[i1, 2], keys[i1, 3], keys2[i2, 2], keys2[i2, 3]], axis=1)
+            uk, inv = np.unique(joined, axis=0, return_inverse=True)
+            tot = np.zeros(len(uk), dtype=np.result_type(vals.dtype, vals2.dtype))
+            np.add.at(tot, inv.reshape(-1), vals[i1] * vals2[i2])
+            keep = tot != 0
+            keys, vals = uk[keep], tot[keep]
+        self.dtype = np.result_type(X.dtype, W.dtype) if W2 is None else np.result_type(X.dtype, W.dtype, W2.dtype)
+        self.qtotal = X.chinfo.make_valid(X.qtotal + W.qtotal + (0 if W2 is None else W2.qtotal))
+        xa = [X.get_leg_index(x_w), X.get_leg_index(x_p)] + ([] if W2 is None else [X.get_leg_index(x_p2)])
+        legs, labels = list(X.legs), list(X.get_leg_labels())
+        legs[xa[0]], labels[xa[0]] = (W if W2 is None else W2).get_leg(w_out), w_out
+        legs[xa[1]], labels[xa[1]] = W.get_leg(p_out), p_out
+        if W2 is not None:
+            legs[xa[2]], labels[xa[2]] = W2.get_leg(p2_out), p2_out
+        perm = [labels.index(l) for l in out_labels]
+        mid = list(range(1, X.rank - 1))
+        assert sorted(xa) == mid and perm[0] == 0 and perm[-1] == X.rank - 1, "X: virtual legs first and last, the MPO step between them"
+        self.legs = [legs[a] for a in perm]
+        self.labels = list(out_labels)
+        # (block, position) of every entry on the legs of X (in) and of Y (out); columns of `keys`: w_in, w_out, p_out, p_in [, p2_out, p2_in]
+        col_in, col_out = [0, 3, 5], [1, 2, 4]
+        b_in, pos_in, b_out, pos_out = {}, {}, {}, {}
+        for n, a in enumerate(xa):
+            b_in[a], pos_in[a] = _leg_block_pos(X.legs[a], keys[:, col_in[n]])
+            b_out[a], pos_out[a] = _leg_block_pos(legs[a], keys[:, col_out[n]])
+        # all (block of X, entry) pairs whose in-blocks agree: a sorted join on the combined block number of the middle legs
+        xq = X._qdata
+        nb = [X.legs[a].block_number for a in mid]
+        key_e, key_x = np.zeros(len(keys), dtype=np.int64), np.zeros(len(xq), dtype=np.int64)
+        for a, n in zip(mid, nb):
+            key_e, key_x = key_e * n + b_in[a], key_x * n + xq[:, a]
+        oe = np.argsort(key_e, kind='stable')
+        lo, hi = np.searchsorted(key_e[oe], key_x, side='left'), np.searchsorted(key_e[oe], key_x, side='right')
+        cnt = hi - lo
+        ib = np.repeat(np.arange(len(xq)), cnt)
+        ie = oe[np.arange(len(ib)) - np.repeat(np.cumsum(cnt) - cnt, cnt) + np.repeat(lo, cnt)]
+        self.empty = len(ib) == 0
+        if self.empty:
+            return
+        oq = xq[ib].copy()
+        for a in mid:
+            oq[:, a] = b_out[a][ie]
+        oq = oq[:, perm]
+        uq, inv = np.unique(oq, axis=0, return_inverse=True)
+        inv = inv.reshape(-1)
+        order = np.lexsort(uq.T)
+        rank_of = np.empty(len(order), dtype=np.int64)
+        rank_of[order] = np.arange(len(order))
+        self.qdata = np.ascontiguousarray(uq[order], dtype=np.intp)
+        blk = rank_of[inv]
+        proto = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
+        sizes = proto._set_blocks(self.qdata, arena=dev.empty(0, self.dtype), qdata_sorted=True)
+        self.offsets = proto._offsets
+        self.total = int(np.sum(sizes))
+        # middle row of the source (order of X's legs) and of the destination (order of out_labels) of every pair
+        shapes_x, sizes_x = X._block_shapes(), X._block_sizes_flat()
+        c = np.zeros(len(ib), dtype=np.int64)
+        for a in mid:
+            c = c * shapes_x[ib, a] + pos_in[a][ie]
+        out_bs = [np.asarray(leg.get_block_sizes(), dtype=np.int64) for leg in self.legs]
+        o = np.zeros(len(ib), dtype=np.int64)
+        for k in range(1, X.rank - 1):
+            o = o * out_bs[k][self.qdata[blk, k]] + pos_out[perm[k]][ie]
+        pre_y, post_y = out_bs[0][self.qdata[:, 0]], out_bs[-1][self.qdata[:, -1]]
+        m_out = sizes // (pre_y * post_y)
+        assert np.array_equal(pre_y * m_out * post_y, sizes)
+        post_x = shapes_x[ib, -1]
+        assert np.array_equal(shapes_x[ib, 0], pre_y[blk]) and np.array_equal(post_x, post_y[blk])
+        m_in = sizes_x[ib] // (shapes_x[ib, 0] * post_x)
+        assert np.all(c < m_in) and np.all(o < m_out[blk])
+        # rows table: the terms of a destination row back to back, in the order of the pairs
+        row_base = np.cumsum(m_out) - m_out
+        row = row_base[blk] + o
+        key = np.lexsort((np.arange(len(row)), row))
+        n_rows = int(np.sum(m_out))
+        counts = np.bincount(row, minlength=n_rows).astype(np.int64)
+        rows = np.stack([np.cumsum(counts) - counts, counts], axis=1)
+        terms = np.zeros((len(key), 4), dtype=np.int64)
+        terms[:, 0] = X._offsets[ib[key]] + c[key] * post_x[key]
+        terms[:, 1] = m_in[key] * post_x[key]
+        alpha = np.asarray(vals[ie[key]], dtype=np.complex128)
+        terms[:, 2] = np.ascontiguousarray(alpha.real).view(np.int64)
+        terms[:, 3] = np.ascontiguousarray(alpha.imag).view(np.int64)
+        # jobs: one per block of Y; with few blocks the rows of a block are split over several jobs (dst_ld = the whole block's rows)
+        pieces = 1 if len(sizes) >= self.SPLIT_BELOW else -(-self.SPLIT_BELOW // len(sizes))
+        per_job = np.maximum(1, -(-m_out // pieces))
+        n_piece = -(-m_out // per_job)
+        jb = np.repeat(np.arange(len(sizes)), n_piece)
+        r0 = (np.arange(len(jb)) - np.repeat(np.cumsum(n_piece) - n_piece, n_piece)) * per_job[jb]
+        jobs = np.zeros((len(jb), 8), dtype=np.int64)
+        jobs[:, 0], jobs[:, 1], jobs[:, 2] = self.offsets[jb] + r0 * post_y[jb], pre_y[jb], np.minimum(per_job[jb], m_out[jb] - r0)
+        jobs[:, 3], jobs[:, 4], jobs[:, 5] = post_y[jb], row_base[jb] + r0, m_out[jb] * post_y[jb]
+        assert len(jobs) <= 60000 and int(np.sum(jobs[:, 1] * jobs[:, 2] * jobs[:, 3])) == self.total
+        self.jobs_host, self.rows_host, self.terms_host, self.sizes = jobs, rows, terms, sizes
+        self.jobs_dev, self.rows_dev, self.terms_dev = dev.to_device(jobs), dev.to_device(rows), dev.to_device(terms)
+        self.n_jobs, self.max_cols = len(jobs), int(np.max(pre_y * post_y))
+        self.x_key = X._struct_key()
+        self.bytes = 8 * (2 if self.dtype.kind == 'c' else 1) * (self.total + int(np.sum(shapes_x[ib, 0] * post_x)))
+
+    def apply(self, X, launch=True):
+        res = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
+        if self.empty:
+            return res
+        if X.dtype != self.dtype:
+            X = X.astype(self.dtype)
+        res._set_blocks(self.qdata, arena=dev.empty(self.total, self.dtype), qdata_sorted=True)
+        if not launch:
+            return res
+        dev.check(dev.lib().tpa_mpo_entry_apply_batch(dev.code(self.dtype), self.jobs_dev.data_ptr(), self.n_jobs, self.rows_dev.data_ptr(),
+                                                      self.terms_dev.data_ptr(), self.max_cols, X._arena.data_ptr(), res._arena.data_ptr(),
+                                                      dev.stream()), "mpo_entry_apply")
+        return res
+
+    def program_op(self, a_slot, c_slot):
+        """The row of a ``tpa_lanczos_run`` program that applies this plan from slot ``a_slot`` into slot ``c_slot`` (kind 6)."""
+        return [6, 0, self.jobs_dev.data_ptr(), self.rows_dev.data_ptr(), self.terms_dev.data_ptr(), self.n_jobs, a_slot, 0, c_slot,
+                self.max_cols, 0, 0]
+
+
+def _envs_wide(LP, RP):
+    """Whether an MPO bond leg of the environments has a block wider than 1."""
+    return not (bool(np.all(LP.get_leg('wR').get_block_sizes() == 1)) and bool(np.all(RP.get_leg('wL').get_block_sizes() == 1)))
+
+
 def _envs_factorable(LP, RP):
-    """LP / RP as the factored forms contract them: the standard labels in an order that needs no transposed copy, MPO bond legs
-    resolved into 1-wide blocks."""
+    """LP / RP as the factored forms contract them: the standard labels with the bra leg of LP before its ket leg and the ket leg of
+    RP before its bra leg; MPO bond legs resolved into 1-wide blocks, or -- where the entry-by-entry MPO step is available
+    (``_entry_route``) -- of any widths (``_env_form`` then makes one transposed copy unless the stored order is the standard one)."""
     lp, rp = list(LP.get_leg_labels()), list(RP.get_leg_labels())
     return (sorted(lp) == sorted(['vR*', 'wR', 'vR']) and lp.index('vR*') < lp.index('vR') and
             sorted(rp) == sorted(['wL', 'vL', 'vL*']) and rp.index('vL') < rp.index('vL*') and
-            bool(np.all(LP.get_leg('wR').get_block_sizes() == 1)) and bool(np.all(RP.get_leg('wL').get_block_sizes() == 1)))
+            (not _envs_wide(LP, RP) or _entry_route(LP.chinfo)))
+
+
+def _env_form(A, labels):
+    """The environment tensor ``A`` with its legs in the order ``labels``: itself, a view when only 1-wide legs move
+    (``_relabel_view``), else -- a wide MPO bond leg has to move -- one transposed copy."""
+    if list(A.get_leg_labels()) == list(labels):
+        return A
+    w = 'wR' if 'wR' in labels else 'wL'
+    if np.all(A.get_leg(w).get_block_sizes() == 1):
+        return _relabel_view(A, labels)
+    return A.transpose(labels)
+
+
+def _factored_plan_class(LP, RP, W, W2=None):
+    """The plan class of the MPO step (``_mpo_plan_class``) if the factored forms can run on these environments, else ``None``:
+    the one acceptance rule of the stand-alone classes and of the module-form dispatch.  Environments with wide MPO bond blocks
+    need the entry-by-entry step (the two older plans move a 1-wide MPO leg only)."""
+    if not _envs_factorable(LP, RP):
+        return None
+    cls = _mpo_plan_class(W, W2)
+    if cls is not MpoEntryApplyPlan and _envs_wide(LP, RP):
+        return None
+    return cls
 
 
 def factored_matvec_possible(LP, RP, W0, W1):
@@ -573,7 +821,7 @@ def factored_matvec_possible(LP, RP, W0, W1):
     MPO bond legs of the environments resolved into 1-wide blocks, leg orders that need no transposed copy.  ``W0`` / ``W1`` with
     labels ``p`` or ``p0`` / ``p1``."""
     w0, w1 = list(W0.get_leg_labels()), list(W1.get_leg_labels())
-    return (_envs_factorable(LP, RP) and _mpo_plan_class(W0, W1) is not None and
+    return (_factored_plan_class(LP, RP, W0, W1) is not None and
             w0 in (['wL', 'wR', 'p0', 'p0*'], ['wL', 'wR', 'p', 'p*']) and w1 in (['wL', 'wR', 'p1', 'p1*'], ['wL', 'wR', 'p', 'p*']))
 
 
@@ -667,8 +915,8 @@ class TwoSiteH(_DeviceEffectiveH):
         self.factored = bool(want) and self._factored_possible()
         if self.factored:       # pipes only (host bookkeeping); LHeff / RHeff are built on first access
             from ..linalg.charges import LegPipe
-            self._LPf = _relabel_view(self.LP, ['vR*', 'wR', 'vR'])      # leg orders the two GEMM steps want (views)
-            self._RPf = _relabel_view(self.RP, ['wL', 'vL', 'vL*'])
+            self._LPf = _env_form(self.LP, ['vR*', 'wR', 'vR'])      # leg orders the two GEMM steps want (views; wide MPO bond legs: a copy)
+            self._RPf = _env_form(self.RP, ['wL', 'vL', 'vL*'])
             self.pipeL = LegPipe([self.LP.get_leg('vR*'), self.W0.get_leg('p0')], qconj=+1)
             self.pipeR = LegPipe([self.W1.get_leg('p1'), self.RP.get_leg('vL*')], qconj=-1)
             self._LHeff = self._RHeff = None
@@ -895,10 +1143,11 @@ class TwoSiteH(_DeviceEffectiveH):
         assert i == self.i0 + 1
         if self.factored:       # LP' = A^dagger (LP . A) W0 without LHeff (reference MPOEnvironment._contract_LP, mpo.py:3087)
             A = U.split_legs(['(vL.p0)'])                                        # vL, p0, vR
-            X = npc.tensordot(self.LP, A, axes=['vR', 'vL'])                     # vR*, wR, p0, vR
-            X = _mpo_plan_class(self.W0).get(X, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'wR', 'vR')).apply(X)
+            cls = _mpo_plan_class(self.W0)
+            X = npc.tensordot(self._LPf if cls is MpoEntryApplyPlan else self.LP, A, axes=['vR', 'vL'])     # vR*, wR, p0, vR
+            X = cls.get(X, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'wR', 'vR')).apply(X)
             LP = npc.tensordot(A.conj(), X, axes=(['vL*', 'p0*'], ['vR*', 'p0']))   # vR*, wR, vR
-            LP = _relabel_view(LP, list(self.LP.get_leg_labels()))
+            LP = _env_form(LP, list(self.LP.get_leg_labels()))
             _env_set_LP(env, i, LP)
             return LP
         LP = npc.tensordot(self.LHeff, U, axes=['(vR.p0*)', '(vL.p0)'])
@@ -911,10 +1160,11 @@ class TwoSiteH(_DeviceEffectiveH):
         assert i == self.i0
         if self.factored:       # RP' = (B . RP) W1 B^dagger without RHeff (reference _contract_RP, mpo.py:3097)
             B = VH.split_legs(['(p1.vR)'])                                       # vL, p1, vR
-            X = npc.tensordot(B, self.RP, axes=['vR', 'vL'])                     # vL, p1, wL, vL*
-            X = _mpo_plan_class(self.W1).get(X, self.W1, 'wL', 'p1', 'wR', 'wL', 'p1', 'p1*', ('vL', 'wL', 'p1', 'vL*')).apply(X)
+            cls = _mpo_plan_class(self.W1)
+            X = npc.tensordot(B, self._RPf if cls is MpoEntryApplyPlan else self.RP, axes=['vR', 'vL'])     # vL, p1, wL, vL*
+            X = cls.get(X, self.W1, 'wL', 'p1', 'wR', 'wL', 'p1', 'p1*', ('vL', 'wL', 'p1', 'vL*')).apply(X)
             RP = npc.tensordot(X, B.conj(), axes=(['p1', 'vL*'], ['p1*', 'vR*']))   # vL, wL, vL*
-            RP = _relabel_view(RP, list(self.RP.get_leg_labels()))
+            RP = _env_form(RP, list(self.RP.get_leg_labels()))
             _env_set_RP(env, i, RP)
             return RP
         RP = npc.tensordot(VH, self.RHeff, axes=['(p1.vR)', '(p1*.vL)'])      # vL, wL, (p1.vL*)
@@ -958,11 +1208,14 @@ class _LocalH(_DeviceEffectiveH):
             _share_mpo_tables(self.W0, W0)               # (host copy of the entries / blocks: cached on the MPO's own tensor)
         self.dtype = dtype
         self._fplans = None
-        self.factored = _envs_factorable(LP, RP) and (W0 is None or (
-            list(self.W0.get_leg_labels()) == ['wL', 'wR', 'p0', 'p0*'] and _mpo_plan_class(self.W0) is not None))
+        if W0 is None:
+            self.factored = _envs_factorable(LP, RP)
+        else:
+            self.factored = (list(self.W0.get_leg_labels()) == ['wL', 'wR', 'p0', 'p0*'] and
+                             _factored_plan_class(LP, RP, self.W0) is not None)
         if self.factored:
-            self._LPf = _relabel_view(LP, ['vR*', 'wR', 'vR'])
-            self._RPf = _relabel_view(RP, ['wL', 'vL', 'vL*'])
+            self._LPf = _env_form(LP, ['vR*', 'wR', 'vR'])
+            self._RPf = _env_form(RP, ['wL', 'vL', 'vL*'])
         n = LP.get_leg('vR').ind_len * RP.get_leg('vL').ind_len
         self.N = n if W0 is None else n * self.W0.get_leg('p0').ind_len
 
@@ -1002,7 +1255,7 @@ class _LocalH(_DeviceEffectiveH):
             if fp['a0'] is not None:
                 T = fp['a0'].apply(T)
             res = fp['p2'].apply(T, self._RPf)
-        else:               # the reference's contractions (MPO bond legs with wider blocks, no charges, empty theta)
+        else:               # the reference's contractions (no blockwise form of the MPO step -- `_mpo_plan_class` --, empty theta)
             res = npc.tensordot(self.LP, theta, axes=['vR', 'vL'])
             if self.W0 is not None:
                 res = npc.tensordot(self.W0, res, axes=[['wL', 'p0*'], ['wR', 'p0']])

@@ -181,6 +181,113 @@ __global__ __launch_bounds__(NT) void mpo_apply_kernel(const MpoJob *__restrict_
     mpo_apply_job<CPLX, D, VEC>(J, T, coeff, src, dst);
 }
 
+// ---- dst slab (pre, n_rows, post) = rows of src slabs, entry by entry: dst row o = sum_t alpha_t * (one middle row of src_t) -----------
+// What it replaces: the same W0 / W1 tensordots as mpo_apply_kernel for MPO tensors that kernel does not serve -- MPO bond legs with
+// blocks wider than 1 (sorted and bunched bond legs), physical sectors wider than TPA_MPO_APPLY_MAXD, no conserved charge: the MPO
+// index then sits INSIDE the memory of a block, and a single entry of W takes one middle row c of a source block (pre, M_in, post) to
+// one middle row o of a destination block (pre, M_out, post).  HBM-bound: a source row is read once per term, every destination
+// element is written once.  The same tables fed to lincomb_kernel would be one job per destination row, 8-byte accesses and a 64-bit
+// division per element; here:
+//   item     = 16 bytes in the VEC form (one complex element, or two real elements j, j + 1 of one row); the scalar form (8-byte
+//              accesses, item = one element) serves base addresses off a 16-byte boundary and, for real data, jobs with an odd post,
+//              dst_off, dst_ld, src_off or src_ld (decided per job from its tables, uniform over the workgroup).
+//   thread   = one column (i, item of j) of its job: it walks the rows o of the job, one accumulator, terms in table order, one chain
+//              of fused multiply-adds per component; one division per column.  j is the fastest index: the loads and stores of a
+//              wavefront are contiguous.  The loads of up to four terms are issued before their multiply-adds.
+//   tables   : the addresses of the row and term entries do not depend on the lane -- uniform (scalar) loads, no LDS.
+//   grid     = (min(512, ceil(max_job_cols / (EPI NT))), n_jobs), EPI = 2 for real data with aligned bases, else 1; grid-stride over
+//              the columns of the job.
+struct EntJob {   // int64[8]
+    int64_t dst_off, pre, n_rows, post, row_begin, dst_ld, pad0, pad1;
+};
+struct EntRow {   // int64[2]
+    int64_t term_begin, term_count;
+};
+
+template <bool CPLX, bool VEC>
+__device__ __forceinline__ double2 ent_load(const double *x) {
+    if (VEC) return *reinterpret_cast<const double2 *>(x);
+    return double2{x[0], CPLX ? x[1] : 0.};
+}
+
+template <bool CPLX, bool VEC>
+__device__ __forceinline__ void ent_fma(double2 &acc, const LinTerm &t, const double2 v) {
+    if (CPLX) {
+        acc.x = fma(t.a_re, v.x, acc.x);
+        acc.x = fma(-t.a_im, v.y, acc.x);
+        acc.y = fma(t.a_re, v.y, acc.y);
+        acc.y = fma(t.a_im, v.x, acc.y);
+    } else {
+        acc.x = fma(t.a_re, v.x, acc.x);
+        if (VEC) acc.y = fma(t.a_re, v.y, acc.y);
+    }
+}
+
+template <bool CPLX, bool VEC>
+__device__ __forceinline__ void mpo_entry_job(const EntJob &J, const EntRow *__restrict__ R, const LinTerm *__restrict__ terms,
+                                              const double *__restrict__ src, double *__restrict__ dst) {
+    constexpr int EPI = (!CPLX && VEC) ? 2 : 1;        // elements per item
+    constexpr int CW = CPLX ? 2 : 1;                   // doubles per element
+    const int n_rows = (int)J.n_rows;
+    const int64_t post_items = J.post / EPI;
+    const int64_t n_cols = J.pre * post_items;
+    const int64_t dst_ld = J.dst_ld ? J.dst_ld : J.n_rows * J.post;
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n_cols; e += (int64_t)gridDim.x * NT) {
+        const int64_t i = e / post_items, j = (e - i * post_items) * EPI;
+        const double *x0 = src + CW * j;
+        double *y = dst + CW * (J.dst_off + i * dst_ld + j);
+        EntRow r = R[0];
+        for (int o = 0; o < n_rows; ++o) {
+            const LinTerm *T = terms + r.term_begin;
+            const int nt = (int)r.term_count;
+            if (o + 1 < n_rows) r = R[o + 1];          // the next row's entry is on its way while this row's terms are read
+            double2 acc{0., 0.};
+            int t = 0;
+            for (; t + 4 <= nt; t += 4) {
+                const double2 v0 = ent_load<CPLX, VEC>(x0 + CW * (T[t].src_off + i * T[t].src_ld));
+                const double2 v1 = ent_load<CPLX, VEC>(x0 + CW * (T[t + 1].src_off + i * T[t + 1].src_ld));
+                const double2 v2 = ent_load<CPLX, VEC>(x0 + CW * (T[t + 2].src_off + i * T[t + 2].src_ld));
+                const double2 v3 = ent_load<CPLX, VEC>(x0 + CW * (T[t + 3].src_off + i * T[t + 3].src_ld));
+                ent_fma<CPLX, VEC>(acc, T[t], v0);
+                ent_fma<CPLX, VEC>(acc, T[t + 1], v1);
+                ent_fma<CPLX, VEC>(acc, T[t + 2], v2);
+                ent_fma<CPLX, VEC>(acc, T[t + 3], v3);
+            }
+            for (; t < nt; ++t) ent_fma<CPLX, VEC>(acc, T[t], ent_load<CPLX, VEC>(x0 + CW * (T[t].src_off + i * T[t].src_ld)));
+            double *yo = y + CW * o * J.post;
+            if (VEC) {
+                *reinterpret_cast<double2 *>(yo) = acc;
+            } else {
+                yo[0] = acc.x;
+                if (CPLX) yo[1] = acc.y;
+            }
+        }
+    }
+}
+
+template <bool CPLX, bool VEC>
+__global__ __launch_bounds__(NT) void mpo_entry_apply_kernel(const EntJob *__restrict__ jobs, const EntRow *__restrict__ rows,
+                                                             const LinTerm *__restrict__ terms, const double *__restrict__ src,
+                                                             double *__restrict__ dst) {
+    const EntJob J = jobs[blockIdx.y];
+    if (J.pre <= 0 || J.n_rows <= 0 || J.post <= 0) return;
+    if ((int64_t)blockIdx.x * NT >= J.pre * J.post) return;      // the grid is sized by the largest job: nothing left for this workgroup
+    const EntRow *R = rows + J.row_begin;
+    if (VEC && !CPLX) {         // two real elements per item: every address of the job has to stay on a 16-byte boundary
+        bool even = ((J.post | J.dst_off | J.dst_ld) & 1) == 0;
+        // every wavefront scans the tables of the job, lane l the rows l, l + 64, ...: the same answer in all of them
+        for (int64_t o = threadIdx.x & 63; o < J.n_rows; o += 64) {
+            const LinTerm *T = terms + R[o].term_begin;
+            for (int64_t t = 0; t < R[o].term_count; ++t) even = even && ((T[t].src_off | T[t].src_ld) & 1) == 0;
+        }
+        if (!__all(even)) {
+            mpo_entry_job<CPLX, false>(J, R, terms, src, dst);
+            return;
+        }
+    }
+    mpo_entry_job<CPLX, VEC>(J, R, terms, src, dst);
+}
+
 struct ScaleJob {  // int64[6]
     int64_t x_off, pre, len, post, s_off, pad;
 };
@@ -363,6 +470,38 @@ extern "C" int tpa_mpo_apply_batch(int dtype, const int64_t *jobs_dev, int n_job
             mpo_apply_launch<true, true>(max_d, grid, st, jobs_dev, terms_dev, coeff_dev, src_base, dst_base);
         else
             mpo_apply_launch<true, false>(max_d, grid, st, jobs_dev, terms_dev, coeff_dev, src_base, dst_base);
+    }
+    TPA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int tpa_mpo_entry_apply_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const int64_t *rows_dev, const int64_t *terms_dev,
+                                         int64_t max_job_cols, const void *src_base, void *dst_base, void *stream) {
+    TPA_ARG_CHECK(dtype == TPA_F64 || dtype == TPA_C128);
+    if (n_jobs <= 0) return 0;
+    TPA_ARG_CHECK(n_jobs <= 65535);
+    const bool aligned = (((uintptr_t)src_base | (uintptr_t)dst_base) & 15) == 0;
+    const int64_t items = (dtype == TPA_F64 && aligned) ? (max_job_cols + 1) / 2 : max_job_cols;
+    int64_t g = (items + NT - 1) / NT;
+    if (g < 1) g = 1;
+    if (g > 512) g = 512;
+    dim3 grid((int)g, n_jobs);
+    hipStream_t st = (hipStream_t)stream;
+    const EntJob *jobs = (const EntJob *)jobs_dev;
+    const EntRow *rows = (const EntRow *)rows_dev;
+    const LinTerm *terms = (const LinTerm *)terms_dev;
+    const double *src = (const double *)src_base;
+    double *dst = (double *)dst_base;
+    if (dtype == TPA_F64) {
+        if (aligned)
+            mpo_entry_apply_kernel<false, true><<<grid, NT, 0, st>>>(jobs, rows, terms, src, dst);
+        else
+            mpo_entry_apply_kernel<false, false><<<grid, NT, 0, st>>>(jobs, rows, terms, src, dst);
+    } else {
+        if (aligned)
+            mpo_entry_apply_kernel<true, true><<<grid, NT, 0, st>>>(jobs, rows, terms, src, dst);
+        else
+            mpo_entry_apply_kernel<true, false><<<grid, NT, 0, st>>>(jobs, rows, terms, src, dst);
     }
     TPA_LAUNCH_CHECK();
     return 0;

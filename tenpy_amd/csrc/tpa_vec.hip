@@ -776,6 +776,11 @@ extern "C" int tpa_lanczos_run_ex(int dtype, int64_t n, const int64_t *ops, int 
                 if (int rc = tpa_mpo_apply_batch(dtype, (const int64_t *)op[2], (int)op[5], (const int64_t *)op[3], (const void *)op[4],
                                                  (int)op[7], op[9], a, c, stream))
                     return rc;
+            } else if (op[0] == 6) {        // MPO step entry by entry (wide MPO bond blocks or wide sectors): p1 = rows, p2 = terms
+                TPA_ARG_CHECK(a != nullptr && c != nullptr);
+                if (int rc = tpa_mpo_entry_apply_batch(dtype, (const int64_t *)op[2], (int)op[5], (const int64_t *)op[3], (const int64_t *)op[4],
+                                                       op[9], a, c, stream))
+                    return rc;
             } else {
                 TPA_ARG_CHECK(false && "unknown op kind");
             }

@@ -1652,6 +1652,7 @@ def clear_device_caches():
         _mc._heff_plans.clear()
         _mc.MpoApplyPlan._cache.clear()
         _mc.MpoBlockApplyPlan._cache.clear()
+        _mc.MpoEntryApplyPlan._cache.clear()
     except ImportError:      # (the linalg package is importable on its own)
         pass
 
