@@ -31,6 +31,14 @@ __all__ = ['TwoSiteDMRGEngine']
 _GC_PAUSE = os.environ.get('TPA_SWEEP_GC_PAUSE', '1') != '0'
 
 
+def _plus_hc(eff_H):
+    """``eff_H + eff_H^dagger`` for an MPO with ``explicit_plus_hc`` (reference mps_common.py:519-520, before the ``orthogonal_to``
+    wrapping): one operator on the direct sum along the MPO bond where ``plus_hc`` offers it, else the sum of the two operators."""
+    from ..linalg.sparse import SumNpcLinearOperator
+    doubled = eff_H.plus_hc()
+    return doubled if doubled is not None else SumNpcLinearOperator(eff_H, eff_H.adjoint())
+
+
 class TwoSiteDMRGEngine:
     def _warm_token(self):
         """Key of this engine's warm-start bases (``linalg/_svd_warm.owner_token``: unique for the life of the engine, released with it)."""
@@ -138,6 +146,9 @@ class TwoSiteDMRGEngine:
             eff_H._sharded_cache = self.__dict__.setdefault('_sharded_plans', {}).setdefault(i0, {})
         else:
             eff_H = TwoSiteH(env, i0, combine=True, move_right=move_right)
+        if getattr(self.H, 'explicit_plus_hc', False):
+            eff_H = _plus_hc(eff_H)
+        if not self.shard_matvec:
             # the contraction plans of this bond's previous visit (same block structure once chi has saturated: checked by their keys)
             cache = self.__dict__.setdefault('_heff_plans', {})
             if eff_H.factored and cache.get(i0) is not None:

@@ -12,12 +12,19 @@
   the middle rows of blocks where MPO bond legs have blocks wider than 1 -- MPOs after ``sort_legcharges`` -- or physical sectors are
   wider than ``TPA_MPO_APPLY_MAXD`` (two sites: their product) (``mps_common.MpoEntryApplyPlan``) -- instead of K = 1
   GEMMs.  Bonds the device form does not cover (sectors below ``MIN_SECTOR``, MPOs without a conserved charge unless
-  ``TPA_MPO_ENTRY_APPLY=2``, ``H + h.c.`` environments, exact diagonalisation of small bonds) get the reference's own class:
-  ``__new__`` dispatches, so the engines see one ``EffectiveH``.
+  ``TPA_MPO_ENTRY_APPLY=2``, the two-thread ``H + h.c.`` environments of ``dmrg_parallel``, exact diagonalisation of small bonds) get
+  the reference's own class: ``__new__`` dispatches, so the engines see one ``EffectiveH``.
 * ``device_one_site_h(RefOneSiteH)`` / ``device_zero_site_h(RefZeroSiteH)`` -> the same for the operators TDVP constructs after
   every two-site / one-site update (``tdvp.py:308 one_site_update``, ``:419 zero_site_update``) on top of
-  ``mps_common.OneSiteH`` / ``ZeroSiteH``; ``combine=True``, ``H + h.c.`` environments, MPO tensors without a blockwise form
+  ``mps_common.OneSiteH`` / ``ZeroSiteH``; ``combine=True``, MPO tensors without a blockwise form
   (``mps_common._mpo_plan_class``: as above) and non-standard labels get the reference's class.
+* ``device_sum_operator(RefSum)`` -> ``SumNpcLinearOperator`` as the engines construct it for MPOs with ``explicit_plus_hc``
+  (``mps_common.py:519``, ``tdvp.py:310``, ``:422``: ``SumNpcLinearOperator(eff_H, eff_H.adjoint())``).  ``adjoint()`` of the three device
+  classes is a token that knows its operator (``mps_common.AdjointH``, with a step-by-step matvec of its own); given a device operator
+  and that operator's own token, the constructor hands back ``eff_H.plus_hc()`` -- ``H_eff + H_eff^dagger`` as ONE device operator on
+  the direct sum along the MPO bond (``mps_common.PlusHcH``: three launches per matvec, a launch program for the native Krylov loops)
+  -- and an ordinary instance in every other case (``stats['plus_hc_device']`` / ``['plus_hc_declined']``).  ``TPA_PLUS_HC=0``: such
+  environments go to the reference's classes as before.
 * ``hinted_mixed_svd(ref_mixed_svd)`` wraps ``TwoSiteDMRGEngine.mixed_svd`` (``dmrg.py:876``) to tell the block SVD which
   bond it decomposes (``np_conserved.svd_hint``), which enables the warm start of ``linalg/_svd_warm.py``.
 """
@@ -30,7 +37,7 @@ from ..linalg import np_conserved as npc
 from ..linalg.charges import DipolarChargeInfo
 from . import mps_common as dev_mc
 
-__all__ = ['device_two_site_h', 'device_one_site_h', 'device_zero_site_h', 'hinted_mixed_svd']
+__all__ = ['device_two_site_h', 'device_one_site_h', 'device_zero_site_h', 'device_sum_operator', 'hinted_mixed_svd']
 
 # Smallest "largest bond sector" for which the device form is used.  Round 3 measurement (module form on the MI355X, Heisenberg
 # L = 100, mixer ramp): with the reference's own class below 64 -- four generic tensordots with transposed copies per matvec,
@@ -38,7 +45,12 @@ __all__ = ['device_two_site_h', 'device_one_site_h', 'device_zero_site_h', 'hint
 # device form everywhere, so the threshold is 1 (kept as a knob for A/B runs).
 MIN_SECTOR = 1
 stats = {'device': 0, 'reference': 0,      # bonds handled by the device form / handed back to the reference's class (TwoSiteH)
-         'device_one': 0, 'reference_one': 0, 'device_zero': 0, 'reference_zero': 0}      # the same for OneSiteH / ZeroSiteH
+         'device_one': 0, 'reference_one': 0, 'device_zero': 0, 'reference_zero': 0,      # the same for OneSiteH / ZeroSiteH
+         # H + h.c. (MPOs with explicit_plus_hc): operators that became one doubled device operator / that did not -- `plus_hc`
+         # declined (the ordinary SumNpcLinearOperator of the device operator and its step-by-step adjoint then), or the device class
+         # handed the bond to the reference's class at construction, which `plus_hc_reference` counts once more on its own;
+         # `plus_hc_other`: sums of anything but a device operator and its own adjoint (the reference's class, unchanged)
+         'plus_hc_device': 0, 'plus_hc_declined': 0, 'plus_hc_reference': 0, 'plus_hc_other': 0}
 
 
 def device_two_site_h(Ref):
@@ -53,12 +65,13 @@ def device_two_site_h(Ref):
                 stats['device'] += 1
                 return object.__new__(cls)
             stats['reference'] += 1
+            _count_hc_reference(env)
             return Ref(env, i0, combine, move_right)          # not an instance of cls: __init__ below is skipped
 
         @staticmethod
         def _device_ok(env, i0, combine):
             try:
-                if getattr(env, 'has_hc', False) or getattr(env.H, 'explicit_plus_hc', False):
+                if not _plain_env(env):
                     return False
                 if isinstance(env.H.chinfo, DipolarChargeInfo) and not env.ket.finite:
                     # dipole charges shift from unit cell to unit cell, which update_LP / update_RP below do not do: the reference's class
@@ -119,16 +132,45 @@ def device_two_site_h(Ref):
             contr = npc.tensordot(contr, self.RP, axes=['wR', 'wL'])
             return contr.combine_legs([['vR*', 'p0', 'p1', 'vL*'], ['vR', 'p0*', 'p1*', 'vL']], qconj=[+1, -1])
 
-        def adjoint(self):
-            raise NotImplementedError("DeviceTwoSiteH is not used for H + h.c. environments (see _device_ok)")
-
     DeviceTwoSiteH.__name__ = 'TwoSiteH'
     DeviceTwoSiteH.__qualname__ = 'TwoSiteH'
     return DeviceTwoSiteH
 
 
 def _plain_env(env):
-    return not (getattr(env, 'has_hc', False) or getattr(env.H, 'explicit_plus_hc', False))
+    """Whether the device classes take this environment: not the two-thread ``H + h.c.`` environments of ``dmrg_parallel`` (``has_hc``),
+    and MPOs with ``explicit_plus_hc`` only while ``mps_common.PLUS_HC`` is on -- the engines then wrap the operator as
+    ``SumNpcLinearOperator(eff_H, eff_H.adjoint())``, which ``device_sum_operator`` turns into ``eff_H.plus_hc()``."""
+    if getattr(env, 'has_hc', False):
+        return False
+    return dev_mc.PLUS_HC or not getattr(env.H, 'explicit_plus_hc', False)
+
+
+def _count_hc_reference(env):
+    if getattr(getattr(env, 'H', None), 'explicit_plus_hc', False) and not getattr(env, 'has_hc', False):
+        stats['plus_hc_reference'] += 1
+        stats['plus_hc_declined'] += 1
+
+
+def device_sum_operator(Ref):
+    class DeviceSumOperator(Ref):
+        __doc__ = ("tenpy.linalg.sparse.SumNpcLinearOperator whose constructor hands back ``op.plus_hc()`` when it is given a device "
+                   "operator and that operator's own adjoint (see tenpy_amd/algorithms/module_form.py).")
+        _reference_class = Ref
+
+        def __new__(cls, orig_operator, other_operator):
+            if isinstance(other_operator, dev_mc.AdjointH) and other_operator.op is orig_operator:
+                doubled = orig_operator.plus_hc()
+                if doubled is not None:
+                    stats['plus_hc_device'] += 1
+                    return doubled                      # not an instance of cls: __init__ is skipped
+                stats['plus_hc_declined'] += 1
+            else:
+                stats['plus_hc_other'] += 1
+            return object.__new__(cls)
+
+    DeviceSumOperator.__name__ = DeviceSumOperator.__qualname__ = 'SumNpcLinearOperator'
+    return DeviceSumOperator
 
 
 def device_one_site_h(Ref):
@@ -144,6 +186,7 @@ def device_one_site_h(Ref):
                 self._tensors = tensors
                 return self
             stats['reference_one'] += 1
+            _count_hc_reference(env)
             return Ref(env, i0, combine, move_right)          # not an instance of cls: __init__ is skipped
 
         @staticmethod
@@ -159,12 +202,10 @@ def device_one_site_h(Ref):
         def __init__(self, env, i0, combine=False, move_right=True):
             LP, W0, RP = self.__dict__.pop('_tensors')
             self.move_right = move_right
+            self._env = env
             self._setup(LP, W0, RP, i0, env.H.dtype)
 
         from_LP_W0_RP = staticmethod(lambda *args, **kwargs: Ref.from_LP_W0_RP(*args, **kwargs))      # (VUMPS: the reference's form)
-
-        def adjoint(self):
-            raise NotImplementedError("DeviceOneSiteH is not used for H + h.c. environments (see _device_ok)")
 
     DeviceOneSiteH.__name__ = DeviceOneSiteH.__qualname__ = 'OneSiteH'
     return DeviceOneSiteH
@@ -184,16 +225,15 @@ def device_zero_site_h(Ref):
                     self._tensors = (LP, RP)
                     return self
             stats['reference_zero'] += 1
+            _count_hc_reference(env)
             return Ref(env, i0)
 
         def __init__(self, env, i0):
             LP, RP = self.__dict__.pop('_tensors')
+            self._env = env
             self._setup(LP, None, RP, i0, env.H.dtype)
 
         from_LP_RP = staticmethod(lambda *args, **kwargs: Ref.from_LP_RP(*args, **kwargs))
-
-        def adjoint(self):
-            raise NotImplementedError("DeviceZeroSiteH is not used for H + h.c. environments (see _device_ok)")
 
     DeviceZeroSiteH.__name__ = DeviceZeroSiteH.__qualname__ = 'ZeroSiteH'
     return DeviceZeroSiteH

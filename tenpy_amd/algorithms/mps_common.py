@@ -904,7 +904,7 @@ class TwoSiteH(_DeviceEffectiveH):
         # the host copy of the MPO entries is cached on the MPO's own tensors (one D2H read per site for the whole run)
         _share_mpo_tables(self.W0, W0)
         _share_mpo_tables(self.W1, W1)
-        self._env = env if tensors is None else None
+        self._env = env         # (with explicit tensors: None, or the holder of the caches of `plus_hc`)
         self._LHeff = self._RHeff = None
         self._plans = None
         self._fplans = None
@@ -1172,6 +1172,15 @@ class TwoSiteH(_DeviceEffectiveH):
         _env_set_RP(env, i, RP)
         return RP
 
+    def adjoint(self):
+        """The Hermitian conjugate as an operator of its own (``AdjointH``: the reference's contractions on the conjugated tensors)."""
+        return AdjointH(self)
+
+    def plus_hc(self):
+        """``self + self.adjoint()`` as ONE operator of this class on the direct sum along the MPO bond (``PlusHcH``), or ``None`` where
+        that form does not apply (``_plus_hc_operator``) -- the caller then sums the two operators itself."""
+        return _plus_hc_operator(self)
+
     def to_matrix_array(self):
         """The effective Hamiltonian contracted to a device matrix with legs [(vL.p0.p1.vR)-like pipe, its conj]
         (reference ``TwoSiteH.to_matrix`` :1392) -- for the exact diagonalisation of small bonds (``full_diag_effH``)."""
@@ -1198,6 +1207,7 @@ class TwoSiteH(_DeviceEffectiveH):
 class _LocalH(_DeviceEffectiveH):
     combine = False
     move_right = True
+    _env = None             # the environment the tensors were taken from, where the constructor knows it (caches of `plus_hc`)
 
     def _setup(self, LP, W0, RP, i0, dtype):
         self.i0 = i0
@@ -1289,6 +1299,13 @@ class _LocalH(_DeviceEffectiveH):
                 res, last = (np.array(ops, dtype=np.int64), bufs, (p1, p2)), p2
         return self._file_program(theta, res, last)
 
+    def adjoint(self):
+        return AdjointH(self)
+
+    def plus_hc(self):
+        """See :meth:`TwoSiteH.plus_hc`."""
+        return _plus_hc_operator(self)
+
     def to_matrix(self):
         """``self`` contracted to a matrix ``[(vR*.p0.vL*), (vR.p0*.vL)]`` (reference :1205-1207, :1520-1521)."""
         contr = self.LP
@@ -1310,6 +1327,7 @@ class OneSiteH(_LocalH):
         if combine:
             raise NotImplementedError("tenpy_amd.OneSiteH (stand-alone driver): only combine=False")
         self.move_right = move_right
+        self._env = env
         self._setup(env.get_LP(i0), env.H.get_W(i0), env.get_RP(i0), i0, env.H.dtype)
 
     @classmethod
@@ -1338,6 +1356,7 @@ class ZeroSiteH(_LocalH):
     acts_on = ['vL', 'vR']
 
     def __init__(self, env, i0):
+        self._env = env
         self._setup(env.get_LP(i0), None, env.get_RP(i0 - 1), i0, env.H.dtype)
 
     @classmethod
@@ -1345,3 +1364,276 @@ class ZeroSiteH(_LocalH):
         self = cls.__new__(cls)
         self._setup(LP.transpose(['vR*', 'wR', 'vR']), None, RP.transpose(['wL', 'vL', 'vL*']), i0, LP.dtype)
         return self
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# H + h.c.: MPOs with ``explicit_plus_hc`` store half of the Hamiltonian, and the engines apply ``H_eff + H_eff^dagger`` (reference
+# mps_common.py:519, tdvp.py:310, :422 -- ``SumNpcLinearOperator(eff_H, eff_H.adjoint())``: two matvecs and an axpy).  The sum is itself an
+# MPO-shaped operator, the direct sum along the MPO bond:
+#     LPd = [LP ; LP^dagger] (stacked on wR),   Wd = W (+) W^dagger (block diagonal in wL, wR),   RPd = [RP ; RP^dagger] (stacked on wL)
+#     LPd . theta . (W0d W1d) . RPd = H theta + H^dagger theta
+# with the tensors of the reference's ``adjoint()`` (:1404-1419, :1210, :1524): ``LP^dagger[vR*, wR, vR] = conj(LP)`` with the two virtual
+# legs exchanged, ``W^dagger[wL, wR, p, p*] = conj(W[wL, wR, p*, p])``.  ``conj()`` flips the ``qconj`` of the MPO bond legs; next to the
+# plain half the adjoint half carries ``leg.conj().flip_charges_qconj()`` -- negated charges, the original ``qconj``.  The stacked legs are
+# unsorted and repeat charges.  1-wide bond blocks stay 1-wide and scalar MPO blocks stay scalar, so everything that exists for a plain
+# operator (the factored matvec and its launch program, the native Krylov loops, the projections of ``OrthogonalNpcLinearOperator``)
+# serves the doubled one through its tables: three launches per matvec, the sum over the two halves inside the accumulation chains of
+# the second GEMM.  ``TPA_PLUS_HC=0``: the routing without all of this.
+PLUS_HC = _os.environ.get('TPA_PLUS_HC', '1') != '0'
+plus_hc_stats = {'env_builds': 0, 'env_hits': 0, 'W_builds': 0}
+_HC_SWAP = {'vR*': 'vR', 'vR': 'vR*', 'vL': 'vL*', 'vL*': 'vL'}
+
+
+def _hc_leg(leg):
+    """The MPO bond leg of an adjoint tensor as it stands next to the plain one: negated charges, the same ``qconj``."""
+    return leg.conj().flip_charges_qconj()
+
+
+def _doubled_leg(leg):
+    """``[leg ; _hc_leg(leg)]``: block ``q`` of the adjoint half is block ``leg.block_number + q``."""
+    return leg.extend(_hc_leg(leg))
+
+
+def _hc_part(A, labels, hc, w_shift=0):
+    """Blocks of ``A`` (``hc``: of its adjoint) as blocks of a tensor with the legs in the order ``labels``: their block indices, and the
+    rows of a ``tpa_copy_batch`` job table without the destination offsets (conjugating, virtual legs exchanged for ``hc``)."""
+    src_ax = [A.get_leg_index(_HC_SWAP.get(l, l) if hc else l) for l in labels]
+    qd = np.array(A._qdata[:, src_ax], dtype=np.intp)
+    w_ax = [k for k, l in enumerate(labels) if l in ('wR', 'wL')][0]
+    qd[:, w_ax] += w_shift
+    shapes = A._block_shapes()
+    M = npc.COPY_MAXDIM
+    jobs = np.zeros((len(qd), 4 + 3 * M), dtype=np.int64)
+    jobs[:, 1], jobs[:, 2], jobs[:, 3] = A._offsets, A.rank, 1 if hc else 0
+    jobs[:, 4:4 + A.rank] = shapes[:, src_ax]
+    jobs[:, 4 + M:4 + M + A.rank] = npc._c_strides(shapes[:, src_ax])
+    jobs[:, 4 + 2 * M:4 + 2 * M + A.rank] = npc._c_strides(shapes)[:, src_ax]
+    return qd, jobs
+
+
+def _hc_assemble(A, legs, labels, parts):
+    """The tensor with ``legs`` whose blocks are those of ``parts`` (``_hc_part``), written by one copy launch per part."""
+    res = npc.Array(legs, A.dtype, A.chinfo.make_valid(), labels)
+    qd = np.concatenate([p[0] for p in parts])
+    order = np.lexsort(qd.T)                # last leg most significant, like every sorted _qdata
+    res._set_blocks(qd[order], qdata_sorted=True)
+    dst = np.empty(len(qd), dtype=np.int64)
+    dst[order] = res._offsets
+    sizes = A._block_sizes_flat()
+    n0 = 0
+    for _, jobs in parts:
+        jobs[:, 0] = dst[n0:n0 + len(jobs)]
+        n0 += len(jobs)
+        npc._run_copy(A.dtype, jobs, int(np.max(sizes)) if len(sizes) else 0, A._arena, res._arena)
+    return res
+
+
+def _hc_env_ok(A, left):
+    """Whether ``A`` is an environment tensor whose adjoint lives on the same legs: standard labels, charge-neutral, the bra leg the
+    conjugate of the ket leg (bra is ket)."""
+    labels = ['vR*', 'wR', 'vR'] if left else ['wL', 'vL', 'vL*']
+    if sorted(A.get_leg_labels()) != sorted(labels) or A.stored_blocks == 0 or np.any(A.qtotal != 0):
+        return False
+    ket, bra = ('vR', 'vR*') if left else ('vL', 'vL*')
+    try:
+        A.get_leg(ket).conj().test_equal(A.get_leg(bra))
+    except ValueError:
+        return False
+    return True
+
+
+def _adjoint_env(A, left):
+    """``LP^dagger`` (``left``) / ``RP^dagger`` of the reference's ``adjoint()`` in the label order of ``A``: the conjugate with the two
+    virtual legs exchanged; its MPO bond leg is ``_hc_leg`` of ``A``'s.  One conjugating, transposing copy launch."""
+    labels = list(A.get_leg_labels())
+    w = 'wR' if left else 'wL'
+    legs = [_hc_leg(leg) if l == w else leg for leg, l in zip(A.legs, labels)]
+    return _hc_assemble(A, legs, labels, [_hc_part(A, labels, True)])
+
+
+def _plus_hc_env(A, left, cache=None, site=None):
+    """``[LP ; LP^dagger]`` stacked on ``wR`` (``left``) / ``[RP ; RP^dagger]`` stacked on ``wL``, in the leg order the factored forms
+    contract (``_envs_factorable``), whatever the stored order of ``A``.  The arena is written by two copy launches: the plain blocks,
+    and the adjoint blocks conjugated and transposed on the way.  ``cache``: dict ``(side, site) -> (A, doubled)`` kept by the caller
+    (the pattern of ``env._heff_cache``); an entry is valid while ``A`` is the tensor it was built from."""
+    key = ('L' if left else 'R', site)
+    hit = cache.get(key) if cache is not None else None
+    if hit is not None and hit[0] is A:
+        plus_hc_stats['env_hits'] += 1
+        return hit[1]
+    labels = ['vR*', 'wR', 'vR'] if left else ['wL', 'vL', 'vL*']
+    w = 'wR' if left else 'wL'
+    legs = [_doubled_leg(A.get_leg(l)) if l == w else A.get_leg(l) for l in labels]
+    res = _hc_assemble(A, legs, labels, [_hc_part(A, labels, False), _hc_part(A, labels, True, A.get_leg(w).block_number)])
+    plus_hc_stats['env_builds'] += 1
+    if cache is not None:
+        cache[key] = (A, res)
+    return res
+
+
+def _plus_hc_W(W):
+    """``W (+) W^dagger``, block diagonal in (wL, wR), for an MPO tensor with the labels ``wL, wR, p, p*``; ``None`` for other labels or a
+    charged tensor.  Built once per MPO tensor on the host and cached on it, so that its host tables (``_tpa_entries``, ``_mpo_blocks``,
+    ``_mpo_coo``) are read once per run as well."""
+    Wd = getattr(W, '_tpa_plus_hc', False)
+    if Wd is False:
+        Wd = None
+        if list(W.get_leg_labels()) == ['wL', 'wR', 'p', 'p*'] and not np.any(W.qtotal != 0) and W.stored_blocks > 0:
+            D = W.to_ndarray()
+            DL, DR = D.shape[:2]
+            full = np.zeros((2 * DL, 2 * DR) + D.shape[2:], dtype=D.dtype)
+            full[:DL, :DR] = D
+            full[DL:, DR:] = D.conj().transpose(0, 1, 3, 2)
+            legs = [_doubled_leg(W.get_leg('wL')), _doubled_leg(W.get_leg('wR')), W.get_leg('p'), W.get_leg('p*')]
+            Wd = npc.Array.from_ndarray(full, legs, dtype=W.dtype, qtotal=W.qtotal, labels=['wL', 'wR', 'p', 'p*'])
+            plus_hc_stats['W_builds'] += 1
+        W._tpa_plus_hc = Wd
+    return Wd
+
+
+class _HeffCacheHolder:
+    """What ``TwoSiteH.combine_Heff`` asks of an environment: the dict of the fused tensors (here: of the doubled operator)."""
+
+    def __init__(self, cache):
+        self._heff_cache = cache
+
+
+def _plus_hc_operator(op):
+    """``PlusHcH`` for the plain operator ``op`` (``TwoSiteH`` / ``OneSiteH`` / ``ZeroSiteH`` or a subclass), or ``None``: switch off,
+    bra is not ket, a charged tensor, mixed dtypes, MPO tensors or environments that the factored forms do not take when doubled."""
+    if not PLUS_HC:
+        return None
+    env = getattr(op, '_env', None)
+    if env is not None and getattr(env, 'bra', None) is not getattr(env, 'ket', None):
+        return None
+    LP, RP = op.LP, op.RP
+    Ws = [W for W in (getattr(op, 'W0', None), getattr(op, 'W1', None)) if W is not None]
+    if not (_hc_env_ok(LP, True) and _hc_env_ok(RP, False)) or LP.dtype != RP.dtype:
+        return None
+    if any(np.result_type(W.dtype, LP.dtype) != LP.dtype for W in Ws):
+        return None
+    Wd = [_plus_hc_W(getattr(W, '_tpa_origin', None) or W) for W in Ws]
+    if any(W is None for W in Wd):
+        return None
+    store = env.__dict__ if env is not None else {}
+    cache = store.setdefault('_plus_hc_cache', {})
+    i0, n = op.i0, op.length
+    LPd = _plus_hc_env(LP, True, cache, i0)
+    RPd = _plus_hc_env(RP, False, cache, i0 + n - 1)
+    if n == 2:
+        factored = bool(getattr(op, 'factored', False))
+        if factored and not factored_matvec_possible(LPd, RPd, *Wd):
+            return None
+        holder = _HeffCacheHolder(store.setdefault('_plus_hc_heff_cache', {}))
+        inner = TwoSiteH(holder, i0, combine=True, move_right=op.move_right, tensors=(LPd, RPd, Wd[0], Wd[1]), factored=factored)
+    else:
+        inner = (OneSiteH if n == 1 else ZeroSiteH).__new__(OneSiteH if n == 1 else ZeroSiteH)
+        inner.move_right = op.move_right
+        inner._setup(LPd, Wd[0] if n == 1 else None, RPd, i0, op.dtype)
+        if not inner.factored:
+            return None
+    return PlusHcH(op, inner)
+
+
+class PlusHcH:
+    """``H_eff + H_eff^dagger`` of a plain effective Hamiltonian as one operator: ``matvec``, ``matvec_program``, ``native_input`` and the
+    flop / byte counts are those of the same class on the doubled tensors (``_plus_hc_operator``); everything else -- ``LP``, ``RP``,
+    ``W0``, ``W1``, ``LHeff``, ``RHeff``, the pipes, ``combine_theta``, ``prepare_svd``, ``update_LP`` / ``update_RP``, ``i0``, ``length``,
+    ``acts_on``, ``combine``, ``move_right`` -- is the plain operator's: the mixers add the h.c. part themselves (reference
+    mps_common.py:2007, :2021, :2158, :2188), and the environments that are stored and updated are the plain ones."""
+
+    def __init__(self, plain, doubled):
+        self.plain = plain
+        self.doubled = doubled
+
+    def __getattr__(self, name):
+        if name in ('plain', 'doubled'):            # (not yet set: unpickling / copy)
+            raise AttributeError(name)
+        return getattr(self.plain, name)
+
+    def matvec(self, theta):
+        labels = theta.get_leg_labels()
+        res = self.doubled.matvec(theta)
+        if list(res.get_leg_labels()) != list(labels):
+            res.itranspose(labels)
+        return res
+
+    def matvec_program(self, theta):
+        return self.doubled.matvec_program(theta)
+
+    def native_input(self, theta, *args, **kwargs):
+        return self.doubled.native_input(theta, *args, **kwargs)
+
+    flops_per_matvec = property(lambda self: getattr(self.doubled, 'flops_per_matvec', None))
+    bytes_per_matvec = property(lambda self: getattr(self.doubled, 'bytes_per_matvec', None))
+
+    @property
+    def _fplans(self):
+        """The contraction plans a driver keeps from visit to visit of a bond: those of the doubled tensors."""
+        return self.doubled._fplans
+
+    @_fplans.setter
+    def _fplans(self, value):
+        self.doubled._fplans = value
+
+    def adjoint(self):
+        return self
+
+    def plus_hc(self):
+        raise ValueError("the operator is H + h.c. already")
+
+    def to_matrix(self):
+        """The plain matrix plus its adjoint, in the form the plain operator returns (host matrix or matrix Array)."""
+        return _plus_adjoint_matrix(self.plain.to_matrix(), +1)
+
+
+def _plus_adjoint_matrix(mat, keep):
+    """``keep * mat + mat^dagger`` for a host matrix or a matrix Array with legs ``[x, x*]``."""
+    if isinstance(mat, np.ndarray):
+        return keep * mat + mat.conj().T
+    adj = mat.conj().itranspose([1, 0])
+    adj.iset_leg_labels(mat.get_leg_labels())
+    return adj if keep == 0 else mat + adj
+
+
+class AdjointH:
+    """The Hermitian conjugate of a plain effective Hamiltonian as an operator of its own, for callers that use it alone (and for
+    ``SumNpcLinearOperator(op, op.adjoint())`` where ``op.plus_hc()`` declines): the reference's contractions (mps_common.py:1146-1149,
+    :1321-1348, :1512-1514) on the conjugated tensors of its ``adjoint()``, step by step, for ``theta`` with the labels of
+    ``op.acts_on``.  Everything but the matvec is looked up on ``op``."""
+
+    def __init__(self, op):
+        self.op = op
+
+    def __getattr__(self, name):
+        if name == 'op':
+            raise AttributeError(name)
+        return getattr(self.op, name)
+
+    def adjoint(self):
+        return self.op
+
+    def native_input(self, theta, *args, **kwargs):
+        return None                 # (the launch program that `__getattr__` would hand out is the plain operator's)
+
+    matvec_program = native_input
+
+    def matvec(self, theta):
+        op = self.op
+        labels = list(theta.get_leg_labels())
+        fused = op.length == 2 and theta.rank == 2
+        if fused:
+            theta = theta.split_legs()
+        res = npc.tensordot(op.LP.conj().ireplace_label('wR*', 'wR'), theta, axes=['vR', 'vL'])
+        for k, W in enumerate([W for W in (getattr(op, 'W0', None), getattr(op, 'W1', None)) if W is not None]):
+            p = 'p%d' % k
+            Wc = W.conj().ireplace_labels(['wL*', 'wR*'], ['wL', 'wR'])
+            res = npc.tensordot(res, Wc, axes=[['wR', p], ['wL', p + '*']])
+        res = npc.tensordot(res, op.RP.conj().ireplace_label('wL*', 'wL'), axes=[['wR', 'vR'], ['wL', 'vL']])
+        res.ireplace_labels(['vR*', 'vL*'], ['vL', 'vR'])
+        if fused:
+            res = op.prepare_svd(res.transpose(['vL', 'p0', 'p1', 'vR']))
+        return res.itranspose(labels)
+
+    def to_matrix(self):
+        return _plus_adjoint_matrix(self.op.to_matrix(), 0)

@@ -138,6 +138,10 @@ class ShardedTwoSiteH(TwoSiteH):
         self.rank = d.get_rank(group)
         self._sharded = None
 
+    def plus_hc(self):
+        """``H + h.c.`` on sharded tensors is not built: the caller sums the operator and its adjoint."""
+        return None
+
     def _factored_possible(self):
         from .mps_common import _mpo_entries
         return _mpo_entries(self.W0) is not None and _mpo_entries(self.W1) is not None and super()._factored_possible()

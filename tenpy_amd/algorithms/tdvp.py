@@ -1,11 +1,11 @@
 """Minimal TDVP drivers for boxes WITHOUT TeNPy (the ``-m gpu`` tests): finite chains, real-time step ``dt``, time-independent
-``H``, no mixer, no ``H + h.c.``.  Where TeNPy is installed, its own ``tenpy.algorithms.tdvp`` engines run unchanged on the device
+``H`` (MPOs with ``explicit_plus_hc``: ``H + h.c.``), no mixer.  Where TeNPy is installed, its own ``tenpy.algorithms.tdvp`` engines run unchanged on the device
 mirror (``tenpy_amd.install.install(fused=True)`` hands them the device ``LanczosEvolution`` / ``OneSiteH`` / ``ZeroSiteH``).
 
 This file only issues the npc calls of the reference's sweeps in the reference's order (tdvp.py:253-315 two-site: evolve theta by
 ``-i dt/2`` -- doubled at the turning bond --, ``svd_theta``, ``set_B`` A / B, environment update, backward one-site evolution by
 ``+i dt/2``; :335-425 single-site: one-site evolve, untruncated SVD, backward zero-site evolution of the bond matrix, absorbed into
-the neighbour in form ``'Th'``).  Options (names as in the reference): ``dt``, ``N_steps``, ``trunc_params``, ``lanczos_params``.
+the neighbour in form ``'Th'``).  Options (names as in the reference): ``dt``, ``N_steps``, ``trunc_params``, ``lanczos_params``, ``preserve_norm``.
 """
 import numpy as np
 
@@ -13,6 +13,7 @@ from ..linalg import np_conserved as npc
 from ..linalg.krylov_based import LanczosEvolution
 from ..linalg.truncation import svd_theta
 from ..networks.mpo import MPOEnvironment
+from .dmrg import _plus_hc
 from .mps_common import OneSiteH, TwoSiteH, ZeroSiteH
 
 __all__ = ['TwoSiteTDVPEngine', 'SingleSiteTDVPEngine']
@@ -33,14 +34,25 @@ class _TDVPEngine:
         self.trunc_err_list = []
 
     def run(self):
-        """Evolve by ``N_steps * dt``."""
+        """Evolve by ``N_steps * dt``.  ``preserve_norm`` (default: real ``dt``) puts ``psi.norm`` back to its value before the steps, as
+        the reference does (algorithm.py:431-442): what a truncation takes off the norm is not decay."""
+        preserve_norm = self.options.get('preserve_norm')
+        if preserve_norm is None:
+            preserve_norm = not np.iscomplex(self.dt)
+        old_norm = self.psi.norm
         for _ in range(self.N_steps):
             self.sweep()
+        if preserve_norm:
+            self.psi.norm = old_norm
         self.evolved_time += self.N_steps * self.dt
         return self.psi
 
     def _krylov_evolve(self, H, theta, dt):
         return LanczosEvolution(H, theta, self.lanczos_params).run(dt, normalize=self.lanczos_params.get('normalize'))
+
+    def _hc(self, eff_H):
+        """The operator the evolution sees: ``eff_H``, plus its h.c. for an MPO with ``explicit_plus_hc`` (reference tdvp.py:310, :422)."""
+        return _plus_hc(eff_H) if getattr(self.H, 'explicit_plus_hc', False) else eff_H
 
     def _site_changed(self, i):
         """Drop every stored environment that contains site ``i``."""
@@ -58,7 +70,7 @@ class TwoSiteTDVPEngine(_TDVPEngine):
 
     def update_local(self, i0, move_right):
         psi, env, i1 = self.psi, self.env, i0 + 1
-        eff_H = TwoSiteH(env, i0, combine=True, move_right=move_right is not False)
+        eff_H = self._hc(TwoSiteH(env, i0, combine=True, move_right=move_right is not False))
         theta = eff_H.combine_theta(psi.get_theta(i0, n=2))
         dt = -0.5j * self.dt
         if i0 == psi.L - 2:
@@ -84,7 +96,7 @@ class TwoSiteTDVPEngine(_TDVPEngine):
         return {'err': err, 'N': N}
 
     def one_site_update(self, i, dt):
-        H1 = OneSiteH(self.env, i, combine=False)
+        H1 = self._hc(OneSiteH(self.env, i, combine=False))
         theta = H1.combine_theta(self.psi.get_theta(i, n=1))
         theta, _ = self._krylov_evolve(H1, theta, dt)
         self.psi.set_B(i, theta.replace_label('p0', 'p'), form='Th')        # (stored environments hold i on neither side here)
@@ -100,7 +112,7 @@ class SingleSiteTDVPEngine(_TDVPEngine):
         self.update_local(0, None)
 
     def update_local(self, i0, move_right):
-        eff_H = OneSiteH(self.env, i0, combine=False, move_right=move_right is not False)
+        eff_H = self._hc(OneSiteH(self.env, i0, combine=False, move_right=move_right is not False))
         theta = eff_H.combine_theta(self.psi.get_theta(i0, n=1))
         dt = -0.5j * self.dt
         if i0 == self.psi.L - 1:
@@ -147,5 +159,5 @@ class SingleSiteTDVPEngine(_TDVPEngine):
 
     def zero_site_update(self, i, theta, dt):
         """Zero-site update of the bond matrix left of site ``i``."""
-        theta, _ = self._krylov_evolve(ZeroSiteH(self.env, i), theta, dt)
+        theta, _ = self._krylov_evolve(self._hc(ZeroSiteH(self.env, i)), theta, dt)
         return theta

@@ -19,7 +19,8 @@ a TeNPy that keeps its own ``np_conserved`` -- is ``tenpy_amd/_npc_helper.py``.
 fused form: ``LanczosGroundState`` (one fused recurrence kernel per step instead of four BLAS-1 calls), ``TwoSiteH``
 (cached plans; factored matvec LP . theta . W0 W1 . RP for ``combine=False``), the bond hint of the warm-started block
 SVD, ``OrthogonalNpcLinearOperator`` (the projections of an excited-state search inside the native Krylov loop), and for TDVP ``LanczosEvolution`` (one native loop and one combination pass per evolution) with the device ``OneSiteH`` /
-``ZeroSiteH``; see :func:`use_fused_callers`.
+``ZeroSiteH``, and ``SumNpcLinearOperator`` (``H + h.c.`` of an MPO with ``explicit_plus_hc`` as one device operator); see
+:func:`use_fused_callers`.
 """
 import importlib
 import importlib.abc
@@ -115,6 +116,11 @@ def use_fused_callers():
       imported by name) -> the device class of ``tenpy_amd/linalg/sparse.py`` (same constructor, same ``gram_schmidt``, same
       ``matvec``), whose ``native_input`` puts the two projections into the launch program of the operator it wraps: the engines'
       ``orthogonal_to=[...]`` runs (excited states) reach the native Krylov loop through the device ``TwoSiteH``.
+    * ``SumNpcLinearOperator`` (``linalg/sparse.py:152``; constructed at ``mps_common.py:520``, ``tdvp.py:311`` and ``:423`` for MPOs with
+      ``explicit_plus_hc``, where it is imported by name) -> ``module_form.device_sum_operator``: a subclass whose constructor hands
+      back ``eff_H.plus_hc()`` -- ``H_eff + H_eff^dagger`` as one device operator -- for a device operator and its own adjoint, and is
+      the reference's class for everything else.  Rebound in ``mps_common`` and ``tdvp`` only (VUMPS and the plane-wave excitations
+      keep theirs).
     """
     import tenpy.algorithms.dmrg as ref_dmrg
     import tenpy.algorithms.mps_common as ref_mc
@@ -146,3 +152,5 @@ def use_fused_callers():
     ref_tdvp.SingleSiteTDVPEngine.EffectiveH = ref_mc.OneSiteH
     if not hasattr(ref_mc.ZeroSiteH, '_reference_class'):
         ref_mc.ZeroSiteH = ref_tdvp.ZeroSiteH = module_form.device_zero_site_h(ref_mc.ZeroSiteH)
+    if not hasattr(ref_mc.SumNpcLinearOperator, '_reference_class'):
+        ref_mc.SumNpcLinearOperator = ref_tdvp.SumNpcLinearOperator = module_form.device_sum_operator(ref_sparse.SumNpcLinearOperator)

@@ -48,10 +48,12 @@ def spinful_fermion_leg(conserve=('N', '2*Sz')):
     raise ValueError("conserve must be ('N', '2*Sz') or ('N',), got %r" % (conserve,))
 
 
-def hubbard_ladder_mpo(Lx, t=1., U=8., mu=0., Ly=2, conserve=('N', '2*Sz'), peierls=0.):
+def hubbard_ladder_mpo(Lx, t=1., U=8., mu=0., Ly=2, conserve=('N', '2*Sz'), peierls=0., explicit_plus_hc=False):
     """MPO of the Ly=2 ladder of length Lx (2 Lx chain sites), D = 10.  ``conserve``: see ``spinful_fermion_leg``.  ``peierls``: the
     hoppings along leg y = 0 get the phase exp(+i peierls), those along y = 1 exp(-i peierls) (a flux of 2 peierls per plaquette;
-    the MPO is complex when it is not zero)."""
+    the MPO is complex when it is not zero).  ``explicit_plus_hc``: the MPO holds half of H and the operator is the MPO plus its h.c.
+    (TeNPy's convention): of every hopping pair only ``c^dag_i c_j`` (i < j) is kept, the on-site terms get half their strength; D = 6,
+    and with ``peierls`` the MPO is complex and not Hermitian."""
     assert Ly == 2
     chinfo, p = spinful_fermion_leg(conserve)
     o = hubbard_ops()
@@ -76,11 +78,15 @@ def hubbard_ladder_mpo(Lx, t=1., U=8., mu=0., Ly=2, conserve=('N', '2*Sz'), peie
             if peierls:                         # c^dag_i c_j (k even) with the phase of its leg, the h.c. term (k odd) with the conjugate
                 leg_t = t * np.exp(1j * peierls * (1 - 2 * (s % 2)) * (1 - 2 * (k % 2)))
             W[5 + k, 9] = -leg_t * second[k]    # leg: partner of the operator placed on site s-2
+        if explicit_plus_hc:
+            W[0, 9] *= 0.5
+            keep = [0, 1, 3, 5, 7, 9]           # the states of k = 0, 2: c^dag_i c_j; k = 1, 3 are their h.c.
+            W = W[np.ix_(keep, keep)]
         Ws.append(W)
     # an operator placed on an odd site must not find a rung partner on the next (even) site: handled above
     # (rung entry only on odd s).  Open boundaries: first / last tensors are the IdL row / IdR column.
     Ws[0] = Ws[0][0:1]
-    Ws[-1] = Ws[-1][:, 9:10]
-    H = mpo_from_dense(Ws, [p] * N, chinfo, dtype=Ws[0].dtype)
+    Ws[-1] = Ws[-1][:, -1:]
+    H = mpo_from_dense(Ws, [p] * N, chinfo, dtype=Ws[0].dtype, explicit_plus_hc=explicit_plus_hc)
     H.IdL, H.IdR = 0, -1
     return H

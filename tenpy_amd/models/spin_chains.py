@@ -29,7 +29,9 @@ def spin_half_leg(conserve='Sz'):
     return chinfo, leg
 
 
-def xxz_chain_mpo(L, Jxx=1., Jz=1., hz=0., conserve='Sz'):
+def xxz_chain_mpo(L, Jxx=1., Jz=1., hz=0., conserve='Sz', explicit_plus_hc=False):
+    """``explicit_plus_hc``: the MPO holds half of H and the operator is the MPO plus its h.c. (TeNPy's convention: of a pair of terms that
+    are each other's h.c. -- ``S+ S-`` / ``S- S+`` -- one is kept, Hermitian terms get half their strength); MPO bond dimension 4."""
     chinfo, p = spin_half_leg(conserve)
     Sp = np.array([[0., 0.], [1., 0.]])    # |up><down| in (down, up) basis: Sp[1,0] = 1
     Sm = Sp.T.copy()
@@ -46,8 +48,12 @@ def xxz_chain_mpo(L, Jxx=1., Jz=1., hz=0., conserve='Sz'):
     W[2, 4] = 0.5 * Jxx * Sp
     W[3, 4] = Jz * Sz
     W[4, 4] = Id
-    Ws = [W[0:1] if i == 0 else (W[:, 4:5] if i == L - 1 else W) for i in range(L)]
-    H = mpo_from_dense(Ws, [p] * L, chinfo)
+    if explicit_plus_hc:
+        W[[0, 3], 4] *= 0.5                     # Hermitian terms: half their strength
+        W = np.delete(np.delete(W, 2, axis=0), 2, axis=1)       # S- S+ is the h.c. of S+ S-
+        D = 4
+    Ws = [W[0:1] if i == 0 else (W[:, D - 1:D] if i == L - 1 else W) for i in range(L)]
+    H = mpo_from_dense(Ws, [p] * L, chinfo, explicit_plus_hc=explicit_plus_hc)
     H.IdL, H.IdR = 0, -1
     return H
 

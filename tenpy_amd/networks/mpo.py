@@ -15,9 +15,9 @@ __all__ = ['MPO', 'MPOEnvironment', 'mpo_from_dense']
 class MPO:
     bc = 'finite'
     finite = True
-    explicit_plus_hc = False
 
-    def __init__(self, p_legs, Ws, IdL=0, IdR=-1):
+    def __init__(self, p_legs, Ws, IdL=0, IdR=-1, explicit_plus_hc=False):
+        self.explicit_plus_hc = bool(explicit_plus_hc)      # the tensors hold half of H: the operator is this MPO plus its h.c. (reference mpo.py:170)
         self.p_legs = list(p_legs)
         self._W = list(Ws)
         self.L = len(Ws)
@@ -33,7 +33,7 @@ class MPO:
         return [W.get_leg('wL').ind_len for W in self._W] + [self._W[-1].get_leg('wR').ind_len]
 
 
-def mpo_from_dense(W_dense_list, p_legs, chinfo, dtype=np.float64, IdL=0, IdR=-1):
+def mpo_from_dense(W_dense_list, p_legs, chinfo, dtype=np.float64, IdL=0, IdR=-1, explicit_plus_hc=False):
     """Build a finite MPO from dense ``W[i]`` of shape (D_l, D_r, d, d).  The charges of the virtual MPO legs are deduced
     from the non-zero entries (every entry must conserve charge) in two passes: forward from the left boundary (index
     ``IdL`` of the first leg = charge 0) and backward from the right boundary (index ``IdR`` of the last leg = charge 0).
@@ -105,7 +105,7 @@ def mpo_from_dense(W_dense_list, p_legs, chinfo, dtype=np.float64, IdL=0, IdR=-1
         W = npc.Array.from_ndarray(Wd, [wL, wR, p, p.conj()], dtype=dtype, qtotal=None if nq == 0 else chinfo.make_valid(),
                                    labels=['wL', 'wR', 'p', 'p*'])
         Ws.append(W)
-    return MPO(p_legs, Ws, IdL, IdR)
+    return MPO(p_legs, Ws, IdL, IdR, explicit_plus_hc=explicit_plus_hc)
 
 
 class MPOEnvironment:
@@ -189,4 +189,7 @@ class MPOEnvironment:
         S = self.psi.get_SR(i0)
         RP = self.get_RP(i0, store=False)
         LP = LP.scale_axis(S, 'vR').scale_axis(np.conj(S), 'vR*')
-        return npc.inner(LP, RP, axes=(['vR*', 'wR', 'vR'], ['vL*', 'wL', 'vL']), do_conj=False)
+        res = npc.inner(LP, RP, axes=(['vR*', 'wR', 'vR'], ['vL*', 'wL', 'vL']), do_conj=False)
+        if getattr(self.H, 'explicit_plus_hc', False):
+            res = res + np.conj(res)        # (reference mpo.py:3083)
+        return res
