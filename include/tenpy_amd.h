@@ -68,6 +68,40 @@ int tpa_gemm_chain(int dtype, int cfg, const int64_t *tasks_dev, const int64_t *
                    const int32_t *tiles_dev, int n_tiles, const void *Abase, const void *Bbase,
                    void *Cbase, void *stream);
 
+/* ---- K1h: grouped, chained, weighted Hermitian rank-k update  (the contraction in the middle of
+ *          DensityMatrixMixer.mix_rho, mps_common.py:2002-2026: rho = X diag(mix) X^dagger per charge sector, which the
+ *          reference forms with conj(), iscale_axis and a general tensordot) -------------------------------------------
+ *        C_t (m x n, row stride ldc)  =  [C_t +]  sum_{l in chain(t)} sum_kk  s_l(kk) * A_l(i,kk) * conj(B_l(j,kk))
+ * links  : int64[n_links][12] = {a_off, b_off, k, a_rs, a_ks, b_rs, b_ks, w_off, w_len, w_inner, 0, 0}
+ *          A_l(i,kk) = Abase[a_off + i*a_rs + kk*a_ks], B_l(j,kk) = Bbase[b_off + j*b_rs + kk*b_ks]; Abase and Bbase may coincide.
+ *          (one of each pair of strides should be 1 for coalescing -- the left mixer has k fast, the right mixer the row; any
+ *          strides are legal)
+ *          s_l(kk) = wvec_dev[w_off + (kk / w_inner) % w_len], a REAL (double) weight whatever the dtype; w_off < 0: s_l = 1 and
+ *          wvec_dev is not read.  w_len >= 1, w_inner >= 1.  A scalar weight per link is w_len = 1 (MPO bond blocks of width 1);
+ *          the modulo form covers an MPO bond block of width w_len that sits anywhere among the contracted legs (w_inner = the
+ *          product of the dimensions of the contracted legs behind it).  The weight is multiplied into A_l(i,kk) first (one
+ *          rounding), the products are summed in MFMA registers.  Zero and negative weights are ordinary data.
+ *          links with k <= 0 are skipped wherever they stand in a chain; a chain without a non-empty link gives C_t = 0
+ *          (accumulate = 0) or leaves C_t as it is (accumulate = 1).  Real data: no conjugation.
+ * tasks  : int64[n_tasks][10] = {c_off, m, n, ldc, link_begin, link_count, accumulate, herm, mirror_off, mirror_ldc}
+ *          herm != 0 (Hermitian task): m == n and A_l == B_l (same base, offset and strides) for every link of the chain.  Only the
+ *          tiles with tile_row >= tile_col are scheduled (a tile above the diagonal is ignored).  The kernel writes C[i,j] for
+ *          i >= j and the mirror C[j,i] = conj(C[i,j]) from the same register, and Im C[i,i] = 0: after the call the m x m block is
+ *          Hermitian bit for bit.  With accumulate = 1 the elements C[i,j], i >= j, are read (the imaginary part of an old diagonal
+ *          element is dropped); the old upper triangle is not.  mirror_off / mirror_ldc are ignored.
+ *          herm == 0 (general task: the rectangle between two different slices of one charge sector): the kernel writes the m x n
+ *          rectangle at c_off and, if mirror_off >= 0, its conjugate transpose (n x m, row stride mirror_ldc) at mirror_off of the
+ *          same arena: M[j,i] = conj(C[i,j]), the value stored at C (after accumulation).  The two rectangles must not overlap.
+ * tiles  : int32[n_tiles][4]  = {task, tile_row, tile_col, 0}; square tiles of tpa_herk_tile_shape(dtype) rows, built on the
+ *          host as for tpa_gemm_chain (longest chains first).  A general task is covered by all of its tiles exactly once, a
+ *          Hermitian task by its tiles on and below the diagonal.  Only the elements of the blocks (and mirrors) are written.
+ * Asynchronous on `stream`; TPA_E_BADARG for a dtype that is neither TPA_F64 nor TPA_C128; n_tiles <= 0 returns 0 without a
+ * launch.  Two identical calls give identical bits.  All three tables and wvec live on the DEVICE.
+ */
+int tpa_herk_tile_shape(int dtype, int *bt);      /* TPA_E_BADARG for another dtype or bt == NULL */
+int tpa_herk_chain(int dtype, const int64_t *tasks_dev, const int64_t *links_dev, const int32_t *tiles_dev, int n_tiles,
+                   const void *Abase, const void *Bbase, const double *wvec_dev, void *Cbase, void *stream);
+
 /* ---- K2-K4: vector kernels over packed arenas (replace ddot/zdotc/zdotu
  *      _npc_helper.pyx:1854-1871, daxpy/zaxpy :316-336, dscal/zscal :339-364,
  *      np.linalg.norm per block np_conserved.py:2252-2255) ------------------------------

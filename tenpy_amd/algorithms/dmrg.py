@@ -4,9 +4,12 @@ Where TeNPy is installed, use TeNPy's own engines on the device mirror instead -
 ``tenpy.algorithms.dmrg.TwoSiteDMRGEngine`` etc. run unchanged (mixers, single-site DMRG, infinite systems, excited states:
 all of it is the reference's code, ``tests/test_reference_suite.py``).  This file only issues the npc calls of one bond update
 in the reference's order (``prepare_update_local`` -> ``update_local`` (Lanczos, ``svd_theta``, ``set_B``) ->
-``update_env``) for finite chains without a mixer, which is exactly BASELINE.json's timed workload.
+``update_env``) for finite chains, which is exactly BASELINE.json's timed workload; with ``mixer`` the density-matrix mixer of
+``algorithms/mixer.py`` takes the place of ``svd_theta`` (reference dmrg.py:914-930).
 
-Options (names as in the reference): ``trunc_params``, ``lanczos_params``, ``chi_list`` (dict sweep -> chi_max);
+Options (names as in the reference): ``trunc_params``, ``lanczos_params``, ``chi_list`` (dict sweep -> chi_max); ``mixer`` (``True`` /
+``'DensityMatrixMixer'`` / ``None``, default ``None``), ``mixer_params`` (``amplitude``, ``decay``, ``disable_after``),
+``chi_list_reactivates_mixer`` (default on: a step of ``chi_list`` switches the mixer on again, reference mps_common.py ``sweep``);
 ``shard_matvec`` (multi-GPU, ``algorithms/sharded.py``; with ``krylov_row_panels`` the Krylov vectors are row panels), ``profile`` (per-phase timers; synchronises the device).
 
 ``orthogonal_to=[MPS, ...]`` (keyword, off by default; not with ``shard_matvec``): the search stays orthogonal to the given states
@@ -72,8 +75,21 @@ class TwoSiteDMRGEngine:
             import os
             if dist.is_initialized() and (dist.get_world_size() > 1 or os.environ.get('TPA_SHARD_FORCE')):
                 self._svd_group = (None, dist.get_rank(), dist.get_world_size())
+        self.mixer = None
+        self._mixer_on = options.get('mixer') not in (None, False)
+        if options.get('mixer') not in (None, False, True, 'DensityMatrixMixer'):
+            raise ValueError("mixer: True, 'DensityMatrixMixer' or None (other mixers: TeNPy's engines on the mirror)")
+        if self._mixer_on and self.shard_matvec:
+            raise ValueError("mixer is not available together with shard_matvec")
+        self.mixer_activate()
         if resume_data is not None:
             self.sweeps = int(resume_data['sweeps'])
+            if self._mixer_on:
+                state = resume_data.get('mixer')
+                self.mixer = None
+                if state is not None:
+                    self.mixer_activate(state['sweep_activated'])
+                    self.mixer.amplitude = state['amplitude']
             for name in ('sweep_stats', 'update_stats'):
                 for k, v in resume_data.get(name, {}).items():
                     getattr(self, name)[k] = list(v)
@@ -82,11 +98,23 @@ class TwoSiteDMRGEngine:
             if resume_data.get('lanczos_params') is not None:
                 self.lanczos_params = dict(resume_data['lanczos_params'])
 
+    def mixer_activate(self, sweep_activated=None):
+        """(Re-)create the mixer from ``mixer_params`` (reference ``Sweep.mixer_activate``)."""
+        if self._mixer_on:
+            from .mixer import DensityMatrixMixer
+            self.mixer = DensityMatrixMixer(self.options.get('mixer_params'), self.sweeps if sweep_activated is None else sweep_activated)
+
+    def mixer_cleanup(self):
+        """After a sweep: let the amplitude decay; drop the mixer when its time is over (reference ``Sweep.mixer_cleanup``)."""
+        if self.mixer is not None:
+            self.mixer = self.mixer.update_amplitude(self.sweeps)
+
     # ---- checkpoint / resume: the state (device arrays pickle through the host), counters, statistics --------------------
     def get_resume_data(self):
         """Not interchangeable with the reference's checkpoints (those hold TeNPy's own MPS class); environments are rebuilt
         from the state on demand."""
-        return {'psi': self.psi, 'sweeps': self.sweeps, 'chi_max': self.trunc_params.get('chi_max'),
+        mixer = None if self.mixer is None else {'amplitude': self.mixer.amplitude, 'sweep_activated': self.mixer.sweep_activated}
+        return {'psi': self.psi, 'sweeps': self.sweeps, 'chi_max': self.trunc_params.get('chi_max'), 'mixer': mixer,
                 'lanczos_params': dict(self.lanczos_params),
                 'sweep_stats': {k: list(v) for k, v in self.sweep_stats.items()},
                 'update_stats': {k: list(v) for k, v in self.update_stats.items()}}
@@ -107,6 +135,9 @@ class TwoSiteDMRGEngine:
             due = [s for s in self.chi_list if s <= self.sweeps]
             if due:
                 self.trunc_params['chi_max'] = self.chi_list[max(due)]
+                # a sweep that is a key of chi_list switches the mixer on again (reference mps_common.py:377-382)
+                if self.sweeps in self.chi_list and self.options.get('chi_list_reactivates_mixer', True):
+                    self.mixer_activate()
         L = self.psi.L
         t0 = time.time()
         worst = 0.
@@ -125,6 +156,7 @@ class TwoSiteDMRGEngine:
             if gc_was_on:
                 gc.enable()
         self.sweeps += 1
+        self.mixer_cleanup()
         st = self.sweep_stats
         st['sweep'].append(self.sweeps)
         st['E'].append(self.update_stats['E_total'][-1])
@@ -154,6 +186,12 @@ class TwoSiteDMRGEngine:
             if eff_H.factored and cache.get(i0) is not None:
                 eff_H._fplans = cache[i0]
         theta = eff_H.combine_theta(psi.get_theta(i0, n=2))
+        self.eff_H = eff_H                                    # (the mixer looks at the operator itself, not at the projected one)
+        if self.mixer is not None:
+            # the HERK tables of this bond's previous visit (validated by the structure keys of their operands, like `_heff_plans`)
+            plain = getattr(eff_H, 'plain', eff_H)           # (H + h.c.: the mixer works on the plain operator behind PlusHcH)
+            if type(plain) is TwoSiteH:
+                plain._mixplans = self.__dict__.setdefault('_mix_plans', {}).setdefault(i0, {})
         if self.ortho_to_envs:
             eff_H = self._wrap_ortho_eff_H(eff_H, i0, theta.get_leg_labels())
         self._tick('heff')
@@ -170,10 +208,16 @@ class TwoSiteDMRGEngine:
         npc.SVD_DIST_GROUP = self._svd_group                  # scoped to this call (other SVDs in the process stay local)
         # warm start of the block SVD: the right (left) singular vectors this bond produced on the previous visit span
         # theta_0 = M . B_{i0+1} (A_{i0} . M) of this one (linalg/_svd_warm.py); consumed by the next npc.svd call
-        npc.svd_hint = ((self._warm_token(), i0), 'R' if move_right else 'L')
+        # (no hint on mixer updates: the decomposition is two eigh of density matrices, not an SVD of theta)
+        npc.svd_hint = ((self._warm_token(), i0), 'R' if move_right else 'L') if self.mixer is None else None
         try:
-            U, S, VH, err, _ = svd_theta(theta, self.trunc_params, qtotal_LR=[psi.get_B(i0, None).qtotal, None],
-                                         inner_labels=['vR', 'vL'])
+            if self.mixer is None:
+                U, S, VH, err, _ = svd_theta(theta, self.trunc_params, qtotal_LR=[psi.get_B(i0, None).qtotal, None],
+                                             inner_labels=['vR', 'vL'])
+            else:       # the side the sweep moves to is mixed; the total charges stay "as before" (reference dmrg.py:925-926)
+                qL = psi.get_B(i0, None).qtotal
+                U, S, VH, err, _ = self.mixer.mix_and_decompose_2site(self, theta, i0, mix_left=move_right, mix_right=not move_right,
+                                                                      qtotal_LR=[qL, theta.chinfo.make_valid(theta.qtotal - qL)])
         finally:
             npc.SVD_DIST_GROUP = previous
             npc.svd_hint = None
@@ -197,7 +241,7 @@ class TwoSiteDMRGEngine:
         us['N_lanczos'].append(N)
         us['time'].append(time.time() - t0)
         us['err'].append(err.eps)
-        us['chi'].append(len(S))
+        us['chi'].append(min(S.shape) if isinstance(S, npc.Array) else len(S))
         return err
 
     def _wrap_ortho_eff_H(self, eff_H, i0, labels):

@@ -37,7 +37,7 @@ from ..linalg import np_conserved as npc
 from ..linalg.charges import DipolarChargeInfo
 from . import mps_common as dev_mc
 
-__all__ = ['device_two_site_h', 'device_one_site_h', 'device_zero_site_h', 'device_sum_operator', 'hinted_mixed_svd']
+__all__ = ['device_two_site_h', 'device_one_site_h', 'device_zero_site_h', 'device_sum_operator', 'hinted_mixed_svd', 'device_mixer_mix_rho']
 
 # Smallest "largest bond sector" for which the device form is used.  Round 3 measurement (module form on the MI355X, Heisenberg
 # L = 100, mixer ramp): with the reference's own class below 64 -- four generic tensordots with transposed copies per matvec,
@@ -50,7 +50,9 @@ stats = {'device': 0, 'reference': 0,      # bonds handled by the device form / 
          # declined (the ordinary SumNpcLinearOperator of the device operator and its step-by-step adjoint then), or the device class
          # handed the bond to the reference's class at construction, which `plus_hc_reference` counts once more on its own;
          # `plus_hc_other`: sums of anything but a device operator and its own adjoint (the reference's class, unchanged)
-         'plus_hc_device': 0, 'plus_hc_declined': 0, 'plus_hc_reference': 0, 'plus_hc_other': 0}
+         'plus_hc_device': 0, 'plus_hc_declined': 0, 'plus_hc_reference': 0, 'plus_hc_other': 0,
+         # DensityMatrixMixer.mix_rho: calls served by `mixer.device_mix_rho` (one tpa_herk_chain launch per side) / by the reference's statements
+         'mixer_device': 0, 'mixer_reference': 0}
 
 
 def device_two_site_h(Ref):
@@ -251,6 +253,27 @@ def hinted_mixed_svd(ref_mixed_svd):
     mixed_svd.__doc__ = ref_mixed_svd.__doc__
     mixed_svd._tpa_wrapped = True
     return mixed_svd
+
+
+def device_mixer_mix_rho(ref_mix_rho):
+    """Wraps ``DensityMatrixMixer.mix_rho`` (mps_common.py:1972-2027) IN PLACE -- the class keeps its identity, so that
+    ``find_subclass(Mixer, name)`` keeps resolving: with a device ``TwoSiteH`` as ``engine.eff_H`` the density matrices come from
+    ``mixer.device_mix_rho``; wherever that declines, and for every other operator, the reference's statements run."""
+    from . import mixer as dev_mixer
+
+    def mix_rho(self, engine, theta, i0, mix_left, mix_right):
+        eff_H = getattr(engine, 'eff_H', None)
+        plain = eff_H.plain if isinstance(eff_H, dev_mc.PlusHcH) else eff_H      # (H + h.c.: the mixer works on the plain operator)
+        if isinstance(plain, dev_mc.TwoSiteH) and getattr(plain, 'i0', None) == i0:
+            got = dev_mixer.device_mix_rho(eff_H, engine.env.H, theta, i0, self.amplitude, mix_left, mix_right)
+            if got is not None:
+                stats['mixer_device'] += 1
+                return got
+        stats['mixer_reference'] += 1
+        return ref_mix_rho(self, engine, theta, i0, mix_left, mix_right)
+    mix_rho.__doc__ = ref_mix_rho.__doc__
+    mix_rho._tpa_wrapped = True
+    return mix_rho
 
 
 def batched_tebd_evolve_step(ref_tebd):

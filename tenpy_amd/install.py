@@ -103,6 +103,8 @@ def use_fused_callers():
       ``tenpy_amd/algorithms/module_form.py`` (cached plans, fused ``LHeff`` build; ``combine=False``: factored matvec), which
       hands bonds it does not cover back to the reference's class;
     * ``TwoSiteDMRGEngine.mixed_svd`` (``dmrg.py:876``) is wrapped to pass the bond index to the block SVD (warm start).
+    * ``DensityMatrixMixer.mix_rho`` (``mps_common.py:1972``) is wrapped in place: with a device ``TwoSiteH`` the density matrices are
+      one ``tpa_herk_chain`` launch per side (``algorithms/mixer.py``), else the reference's statements.
     * ``TEBDEngine.evolve_step`` (``tebd.py:374``; inherited by ``QRBasedTEBDEngine``) -> the bonds of a half-step decomposed in one
       batched device call (``module_form.batched_tebd_evolve_step``; the per-bond statements stay the reference's).
     * ``LanczosEvolution`` (``linalg/krylov_based.py:718``; constructed at ``tdvp.py:132 _krylov_evolve``) -> the device class: the
@@ -139,6 +141,8 @@ def use_fused_callers():
         ref_dmrg.TwoSiteDMRGEngine.EffectiveH = dev_cls
     if not getattr(ref_dmrg.TwoSiteDMRGEngine.mixed_svd, '_tpa_wrapped', False):
         ref_dmrg.TwoSiteDMRGEngine.mixed_svd = module_form.hinted_mixed_svd(ref_dmrg.TwoSiteDMRGEngine.mixed_svd)
+    if not getattr(ref_mc.DensityMatrixMixer.mix_rho, '_tpa_wrapped', False):
+        ref_mc.DensityMatrixMixer.mix_rho = module_form.device_mixer_mix_rho(ref_mc.DensityMatrixMixer.mix_rho)
     import tenpy.algorithms.tebd as ref_tebd
     if not getattr(ref_tebd.TEBDEngine.evolve_step, '_tpa_wrapped', False):
         ref_tebd.TEBDEngine.evolve_step = module_form.batched_tebd_evolve_step(ref_tebd)

@@ -48,7 +48,7 @@ class MPS:
 
     @property
     def chi(self):
-        return [len(s) for s in self._S[1:-1]]
+        return [min(s.shape) if isinstance(s, npc.Array) else len(s) for s in self._S[1:-1]]
 
     def get_SL(self, i):
         return self._S[i]
@@ -57,10 +57,12 @@ class MPS:
         return self._S[i + 1]
 
     def set_SL(self, i, S):
-        self._S[i] = np.asarray(S)
+        """1D singular values, or -- while a mixer is on -- the general 2D bond matrix (Array, labels 'vL', 'vR'; reference
+        mps.py ``set_SL``), which is kept as it is."""
+        self._S[i] = S if isinstance(S, npc.Array) else np.asarray(S)
 
     def set_SR(self, i, S):
-        self._S[i + 1] = np.asarray(S)
+        self._S[i + 1] = S if isinstance(S, npc.Array) else np.asarray(S)
 
     def set_B(self, i, B, form='B'):
         self._B[i] = B.transpose(['vL', 'p', 'vR']) if B._labels != ['vL', 'p', 'vR'] else B
@@ -70,6 +72,13 @@ class MPS:
     def _scaled(B, S, power, axis):
         if power == 0.:
             return B
+        if isinstance(S, npc.Array):        # a 2D bond matrix multiplies; its inverse or root is not available (as in the reference)
+            if power != 1.:
+                raise ValueError("a 2D bond matrix S can only be applied with power +1, got %r" % (power,))
+            if axis == 'vL':
+                return npc.tensordot(S, B, axes=['vR', 'vL'])
+            res = npc.tensordot(B, S, axes=['vR', 'vL'])
+            return res.transpose(B.get_leg_labels()) if list(res.get_leg_labels()) != list(B.get_leg_labels()) else res
         return B.scale_axis(S if power == 1. else S**power, axis)
 
     def get_B(self, i, form='B', copy=False):
@@ -124,6 +133,9 @@ class MPS:
     def entanglement_entropy(self):
         res = []
         for s in self._S[1:-1]:
+            if isinstance(s, npc.Array):    # the singular values of a 2D bond matrix
+                s = np.asarray(npc.svd(s, compute_uv=False))
+                s = s / np.linalg.norm(s)
             p = s[s > 1e-30]**2
             res.append(float(-np.sum(p * np.log(p))))
         return np.array(res)
