@@ -94,7 +94,7 @@ def main():
 
     def route_b():
         T1 = npc.tensordot(fac._LPf, theta4, axes=['vR', 'vL'])            # X exactly as (c) builds it: the GEMM plan, then MpoApplyPlan
-        X = mixer._apply_mpo(T1, fac.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'wR', 'p1', 'vR'))
+        X = mixer._apply_mpo(T1, fac.W0, True, ('vR*', 'p0', 'wR', 'p1', 'vR'))
         rho_L = npc.tensordot(X.scale_axis(mix_L, 'wR'), X.conj(), axes=[['wR', 'p1', 'vR'], ['wR*', 'p1*', 'vR*']])
         rho_R = npc.tensordot(theta2.conj(), theta2, axes=['(vL*.p0*)', '(vL.p0)'])
         return rho_L, rho_R

@@ -69,7 +69,6 @@ class _Source:
     @property
     def key(self):
         return (self.X._struct_key(), self.n_row, self.rows_first, self.w_axis)
-        self.fused = n_row == 1
 
 
 class RhoPlan:
@@ -183,13 +182,14 @@ def _rho(eff_H, side, pipe, Xs, sources, weights, labels, dtype, handover):
     return plan.apply(pipe, Xs, weights, labels)
 
 
-def _apply_mpo(T, W, x_w, x_p, w_in, w_out, p_out, p_in, out_labels):
-    """One MPO tensor applied to ``T`` with the other physical leg as a spectator.  ``MpoApplyPlan`` (MPO blocks that are single
-    numbers) works on whole blocks of ``T`` whatever its further legs: one ``tpa_lincomb_batch`` launch, written in the leg order the
-    HERK wants.  The block and entry plan classes lay out their jobs for the legs of a one-site vector; for those MPOs X is the
-    generic ``tensordot`` and a transposing copy."""
+def _apply_mpo(T, W, left, out_labels):
+    """One MPO tensor applied to ``T`` with the other physical leg as a spectator: W0 going left to right (``left``), else W1 going
+    right to left.  ``MpoApplyPlan`` (MPO blocks that are single numbers) works on whole blocks of ``T`` whatever its further legs: one
+    ``tpa_lincomb_batch`` launch, written in the leg order the HERK wants.  The block and entry plan classes lay out their jobs for
+    the legs of a one-site vector; for those MPOs X is the generic ``tensordot`` and a transposing copy."""
     if mps_common._mpo_plan_class(W) is mps_common.MpoApplyPlan:
-        return mps_common.MpoApplyPlan.get(T, W, x_w, x_p, w_in, w_out, p_out, p_in, tuple(out_labels)).apply(T)
+        return (mps_common._mpo_step_lr if left else mps_common._mpo_step_rl)(T, W, out_labels=out_labels).apply(T)
+    x_w, x_p, w_in, _, _, p_in = mps_common._STEP_LR if left else mps_common._STEP_RL
     return npc.tensordot(T, W, axes=([x_w, x_p], [w_in, p_in])).transpose(list(out_labels))
 
 
@@ -246,7 +246,7 @@ def device_mix_rho(eff_H, H, theta, i0, amplitude, mix_left, mix_right, weights=
     if mix_left:
         if eff_H.factored:
             T1 = npc.tensordot(eff_H._LPf, th4, axes=['vR', 'vL'])              # vR*, wR, p0, p1, vR  (contracted index: chi)
-            X = _apply_mpo(T1, eff_H.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'wR', 'p1', 'vR'))
+            X = _apply_mpo(T1, eff_H.W0, True, ('vR*', 'p0', 'wR', 'p1', 'vR'))
             src = _Source(X, 2, True, 2)
         else:
             X = npc.tensordot(eff_H.LHeff, th2, axes=['(vR.p0*)', '(vL.p0)'])    # (vR*.p0), wR, (p1.vR): the first GEMM of the matvec
@@ -261,7 +261,7 @@ def device_mix_rho(eff_H, H, theta, i0, amplitude, mix_left, mix_right, weights=
     if mix_right:
         if eff_H.factored:
             T1 = npc.tensordot(th4, eff_H._RPf, axes=['vR', 'vL'])              # vL, p0, p1, wL, vL*
-            X = _apply_mpo(T1, eff_H.W1, 'wL', 'p1', 'wR', 'wL', 'p1', 'p1*', ('vL', 'p0', 'wL', 'p1', 'vL*'))
+            X = _apply_mpo(T1, eff_H.W1, False, ('vL', 'p0', 'wL', 'p1', 'vL*'))
             src = _Source(X, 2, False, 2)
         else:
             X = npc.tensordot(th2, eff_H.RHeff, axes=['(p1.vR)', '(p1*.vL)'])    # (vL.p0), wL, (p1.vL*)

@@ -80,6 +80,60 @@ def _mpo_entries(W):
     return ent
 
 
+def _mpo_blocks(W):
+    """(qdata, host copies of the stored blocks) of an MPO tensor whose two MPO bond legs have 1-wide blocks and whose physical charge
+    sectors are at most ``TPA_MPO_APPLY_MAXD`` wide, else ``None`` (cached on W like ``_tpa_entries``).  Wider bond blocks or sectors
+    go entry by entry (``_mpo_coo`` / ``MpoEntryApplyPlan``), and so do MPOs without a conserved charge -- one dense block, no charge
+    rule to select the terms -- where ``ENTRY_APPLY`` is 2; by default they keep the reference's contractions."""
+    blk = getattr(W, '_tpa_blocks', False)
+    if blk is False:
+        labels = list(W.get_leg_labels())
+        blk = None
+        if W.rank == 4 and 'wL' in labels and 'wR' in labels and W.stored_blocks > 0 and W.chinfo.qnumber > 0:
+            phys = [a for a in range(4) if labels[a] not in ('wL', 'wR')]
+            if all(np.all(W.get_leg(l).get_block_sizes() == 1) for l in ('wL', 'wR')) and \
+                    all(int(np.max(W.legs[a].get_block_sizes())) <= MPO_APPLY_MAXD for a in phys):
+                blk = (np.array(W._qdata), [np.array(b) for b in W._data])
+        W._tpa_blocks = blk
+    return blk
+
+
+def _share_mpo_tables(W_new, W):
+    """Hand the host tables cached on the MPO's own tensor ``W`` to its relabelled copy ``W_new`` (one D2H read per site and run)."""
+    W_new._tpa_entries = _mpo_entries(W)
+    if W_new._tpa_entries is None and BLOCK_APPLY and dev.lib_provides('tpa_mpo_apply_batch'):
+        W_new._tpa_blocks = _mpo_blocks(W)
+    W_new._tpa_origin = W       # (``_mpo_coo`` reads and caches its table there when a plan first asks for it)
+
+
+def _mpo_coo(W):
+    """(global indices int64[n, 4] in the stored leg order, values) of the nonzero entries of an MPO tensor with legs ``wL``, ``wR``
+    and two physical legs, whatever the widths of its blocks; ``None`` for anything else (cached on W like ``_tpa_entries``)."""
+    coo = getattr(W, '_tpa_coo', False)
+    if coo is False and getattr(W, '_tpa_origin', None) is not None:      # a relabelled copy: the table of the MPO's own tensor
+        coo = W._tpa_coo = _mpo_coo(W._tpa_origin)
+    if coo is False:
+        labels = list(W.get_leg_labels())
+        coo = None
+        if W.rank == 4 and 'wL' in labels and 'wR' in labels and W.stored_blocks > 0:
+            idx, vals = [], []
+            for q, b in zip(np.array(W._qdata).tolist(), W._data):
+                b = np.array(b)
+                nz = np.nonzero(b)
+                idx.append(np.stack([nz[a] + int(W.legs[a].slices[q[a]]) for a in range(4)], axis=1))
+                vals.append(b[nz])
+            coo = (np.concatenate(idx).astype(np.int64).reshape(-1, 4), np.concatenate(vals))
+        W._tpa_coo = coo
+    return coo
+
+
+def _pack_alpha(terms, alpha):
+    """The coefficients ``alpha`` as the bits of their real and imaginary parts in columns 2 and 3 of the int64 table ``terms``."""
+    alpha = np.asarray(alpha, dtype=np.complex128)
+    terms[:, 2] = np.ascontiguousarray(alpha.real).view(np.int64)
+    terms[:, 3] = np.ascontiguousarray(alpha.imag).view(np.int64)
+
+
 def _lincomb_into(dst, src, jobs, terms, max_elems):
     if len(jobs) == 0:
         return
@@ -89,6 +143,25 @@ def _lincomb_into(dst, src, jobs, terms, max_elems):
         jd = dev.table(jobs[s0:s0 + 60000])
         dev.check(L.tpa_lincomb_batch(dev.code(dst.dtype), jd.data_ptr(), len(jobs[s0:s0 + 60000]), terms_d.data_ptr(),
                                       int(max_elems), src._arena.data_ptr(), dst._arena.data_ptr(), dev.stream()), "lincomb")
+
+
+def _rank_rows(q):
+    """The distinct rows of ``q`` in the order of a sorted ``_qdata`` (last column most significant), and for every row of ``q`` its
+    number in that order."""
+    uq, inv = np.unique(q, axis=0, return_inverse=True)
+    order = np.lexsort(uq.T)
+    rank_of = np.empty(len(order), dtype=np.int64)
+    rank_of[order] = np.arange(len(order))
+    return uq[order], rank_of[inv.reshape(-1)]
+
+
+def _group_terms(dst):
+    """Terms grouped by their destination ``dst`` (a block number or an offset), in a fixed order: the sorting permutation and, in the
+    sorted order, the first term and the number of terms of every destination (one job each)."""
+    key = np.lexsort((np.arange(len(dst)), dst))
+    d_sorted = dst[key]
+    starts = np.nonzero(np.concatenate([[True], d_sorted[1:] != d_sorted[:-1]]))[0]
+    return key, starts, np.diff(np.concatenate([starts, [len(key)]]))
 
 
 from collections import OrderedDict as _OrderedDict
@@ -158,34 +231,21 @@ def _fused_heff(env_t, W, left):
     Qr, Qc = qm[r_row, 2], qm[c_row, 2]
     r0, c0 = qm[r_row, 0], qm[c_row, 0]
     bq = np.stack([Qr, w_out, Qc], axis=1) if left else np.stack([w_out, Qr, Qc], axis=1)
-    ubq, inv = np.unique(bq, axis=0, return_inverse=True)
-    inv = inv.reshape(-1)
-    order = np.lexsort(ubq.T)                       # last leg most significant, like every sorted _qdata
-    rank_of = np.empty(len(order), dtype=np.int64)
-    rank_of[order] = np.arange(len(order))
-    ubq = ubq[order]
-    blk = rank_of[inv]
+    ubq, blk = _rank_rows(bq)
     res = npc.Array(legs, env_t.dtype, env_t.chinfo.make_valid(env_t.qtotal + W.qtotal), labels)
-    sizes = res._set_blocks(ubq, zero=True, qdata_sorted=True)
+    res._set_blocks(ubq, zero=True, qdata_sorted=True)
     ld = psz[Qc]
     dst_off = res._offsets[blk] + r0 * ld + c0
     # one job per destination slab, its terms = all contributions landing there (deterministic order)
-    key = np.stack([dst_off, np.arange(len(dst_off))], axis=1)
-    perm = np.lexsort((key[:, 1], key[:, 0]))
-    d_sorted = dst_off[perm]
-    first = np.concatenate([[True], d_sorted[1:] != d_sorted[:-1]])
-    starts = np.nonzero(first)[0]
-    counts = np.diff(np.concatenate([starts, [len(perm)]]))
+    perm, starts, counts = _group_terms(dst_off)
     jobs = np.zeros((len(starts), 8), dtype=np.int64)
     pf = perm[starts]
-    jobs[:, 0], jobs[:, 1], jobs[:, 2], jobs[:, 3] = d_sorted[starts], rows[pf], cols[pf], ld[pf]
+    jobs[:, 0], jobs[:, 1], jobs[:, 2], jobs[:, 3] = dst_off[pf], rows[pf], cols[pf], ld[pf]
     jobs[:, 4], jobs[:, 5] = starts, counts
     terms = np.zeros((len(perm), 4), dtype=np.int64)
     terms[:, 0] = env_t._offsets[ie[perm]]
     terms[:, 1] = shapes[ie[perm], 2]
-    alpha = np.asarray(wv[iw[perm]], dtype=np.complex128)
-    terms[:, 2] = np.ascontiguousarray(alpha.real).view(np.int64)
-    terms[:, 3] = np.ascontiguousarray(alpha.imag).view(np.int64)
+    _pack_alpha(terms, wv[iw[perm]])
     _lincomb_into(res, env_t, jobs, terms, int(np.max(rows * cols)))
     if 0 < len(jobs) <= 60000:
         for arr in (res._qdata, res._offsets):
@@ -240,7 +300,83 @@ def _relabel_view(A, labels):
     return B
 
 
-class MpoApplyPlan:
+class _MpoStepPlan:
+    """What the three plans of the MPO step share -- ``MpoApplyPlan`` (scalar MPO blocks), ``MpoBlockApplyPlan`` (small matrices) and
+    ``MpoEntryApplyPlan`` (entry by entry): the cached constructor, the bookkeeping of the result Y and ``apply``.  A subclass has a
+    ``_cache`` dict of its own (``npc.clear_device_caches`` clears them by class), ``_table(W)``, the reader of the host table of an MPO
+    tensor that its job tables are built from, ``_launch(X, res)``, the call of its kernel, and ``program_op``."""
+
+    @classmethod
+    def get(cls, X, W, *args, W2=None, **kwargs):
+        """Cached constructor: the plan depends on the block structure of X and on the MPO tensors only."""
+        t1, t2 = cls._table(W), (None if W2 is None else cls._table(W2))
+        key = (X._struct_key(), str(X.dtype), id(t1), None if t2 is None else id(t2), args,
+               tuple(sorted(kwargs.items())), tuple(X.get_leg_labels()))
+        plan = cls._cache.get(key)
+        if plan is None or plan._tables_alive[0] is not t1 or plan._tables_alive[1] is not t2:
+            if len(cls._cache) > 4096:
+                cls._cache.clear()
+            plan = cls._cache[key] = cls(X, W, *args, W2=W2, **kwargs)
+            # the key holds id()s: keep the host tables alive as long as the plan is cached, so that the id of a dead
+            # MPO's table can never be handed to a new one (a stale plan would apply the OLD couplings)
+            plan._tables_alive = (t1, t2)
+        return plan
+
+    @staticmethod
+    def _match_blocks(X, keys, xa):
+        """All (block of X, term) pairs for terms with the block indices ``keys`` = (w_in, w_out, p_out, p_in [, p2_out, p2_in]) that
+        act on the legs ``xa`` of X: the block of X and the term of every pair, and its block indices in Y (in the leg order of X)."""
+        xq = X._qdata
+        match = xq[:, xa[0]][:, None] == keys[None, :, 0]
+        for a, col in zip(xa[1:], (3, 5)):
+            match &= xq[:, a][:, None] == keys[None, :, col]
+        ib, ie = np.nonzero(match)
+        oq = xq[ib].copy()
+        for a, col in zip(xa, (1, 2, 4)):
+            oq[:, a] = keys[ie, col]
+        return ib, ie, oq
+
+    def _set_output(self, X, W, W2, xa, w_out, p_out, p2_out, out_labels):
+        """``dtype``, ``qtotal``, ``legs`` and ``labels`` of Y: those of X with the legs ``xa`` (MPO leg, physical leg [, second physical
+        leg]) replaced by the open legs of W (, W2), in the order ``out_labels``.  Returns the legs in the order of X and ``perm``, the
+        position in X of every leg of Y."""
+        self.dtype = np.result_type(X.dtype, W.dtype) if W2 is None else np.result_type(X.dtype, W.dtype, W2.dtype)
+        self.qtotal = X.chinfo.make_valid(X.qtotal + W.qtotal + (0 if W2 is None else W2.qtotal))
+        legs, labels = list(X.legs), list(X.get_leg_labels())
+        legs[xa[0]], labels[xa[0]] = (W if W2 is None else W2).get_leg(w_out), w_out
+        legs[xa[1]], labels[xa[1]] = W.get_leg(p_out), p_out
+        if W2 is not None:
+            legs[xa[2]], labels[xa[2]] = W2.get_leg(p2_out), p2_out
+        perm = [labels.index(l) for l in out_labels]
+        self.legs = [legs[a] for a in perm]
+        self.labels = list(out_labels)
+        return legs, perm
+
+    def _rank_blocks(self, oq):
+        """``qdata``, ``offsets`` and ``total`` of Y from ``oq``, the block indices in Y of every (block of X, term of W) pair.  Returns
+        the block number in Y of every pair and the block sizes of Y."""
+        uq, blk = _rank_rows(oq)
+        self.qdata = np.ascontiguousarray(uq, dtype=np.intp)
+        proto = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
+        sizes = proto._set_blocks(self.qdata, arena=dev.empty(0, self.dtype), qdata_sorted=True)
+        self.offsets = proto._offsets
+        self.total = int(np.sum(sizes))
+        return blk, sizes
+
+    def apply(self, X, launch=True):
+        """Y as a new Array; ``launch=False``: its block structure and an unwritten arena only (a launch program is being assembled)."""
+        res = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
+        if self.empty:
+            return res
+        if X.dtype != self.dtype:
+            X = X.astype(self.dtype)
+        res._set_blocks(self.qdata, arena=dev.empty(self.total, self.dtype), qdata_sorted=True)
+        if launch:
+            self._launch(X, res)
+        return res
+
+
+class MpoApplyPlan(_MpoStepPlan):
     """``Y[.., w', p, ..] = sum_{w, p'} W[w, w', p, p'] X[.., w, p', ..]`` for an MPO tensor whose blocks are single
     numbers: every block of Y is a linear combination of whole blocks of X (the w and p legs of X have 1-wide blocks, so
     a block of X and the blocks of Y it feeds have the same memory layout).  One ``tpa_lincomb_batch`` launch; the job
@@ -253,107 +389,46 @@ class MpoApplyPlan:
     ``out_labels``                : order of the legs of Y (must keep the relative order of X's non-trivial legs).
     """
     _cache = {}
-
-    @classmethod
-    def get(cls, X, W, *args, W2=None, **kwargs):
-        """Cached constructor: the plan depends on the block structure of X and on the MPO tensors only."""
-        e1, e2 = _mpo_entries(W), (None if W2 is None else _mpo_entries(W2))
-        key = (X._struct_key(), str(X.dtype), id(e1), None if e2 is None else id(e2), args,
-               tuple(sorted(kwargs.items())), tuple(X.get_leg_labels()))
-        plan = cls._cache.get(key)
-        if plan is None or plan._entries_alive[0] is not e1 or plan._entries_alive[1] is not e2:
-            if len(cls._cache) > 4096:
-                cls._cache.clear()
-            plan = cls._cache[key] = cls(X, W, *args, W2=W2, **kwargs)
-            # the key holds id()s: keep the entry tables alive as long as the plan is cached, so that the id of a dead
-            # MPO's table can never be handed to a new one (a stale plan would apply the OLD couplings)
-            plan._entries_alive = (e1, e2)
-        return plan
+    _table = staticmethod(_mpo_entries)
 
     def __init__(self, X, W, x_w, x_p, w_in, w_out, p_out, p_in, out_labels, W2=None, x_p2=None, p2_out=None, p2_in=None):
-        ent = _mpo_entries(W)
+        ent = self._table(W)
         assert ent is not None
         wq, wv = ent
         wl = list(W.get_leg_labels())
-        ci, co, po, pi = wl.index(w_in), wl.index(w_out), wl.index(p_out), wl.index(p_in)
-        xa_w, xa_p = X.get_leg_index(x_w), X.get_leg_index(x_p)
-        assert np.all(X.legs[xa_w].get_block_sizes() == 1) and np.all(X.legs[xa_p].get_block_sizes() == 1)
+        xa = [X.get_leg_index(l) for l in ((x_w, x_p) if W2 is None else (x_w, x_p, x_p2))]
+        assert all(np.all(X.legs[a].get_block_sizes() == 1) for a in xa)
         # entry table: (w_in, w_out, p_out, p_in [, p2_out, p2_in]) -> value
-        e_in_w, e_out_w, e_po, e_pi, e_val = wq[:, ci], wq[:, co], wq[:, po], wq[:, pi], np.asarray(wv)
-        e_p2o = e_p2i = None
-        w_leg_out, xa_p2 = W.get_leg(w_out), None
+        keys, vals = wq[:, [wl.index(l) for l in (w_in, w_out, p_out, p_in)]], np.asarray(wv)
         if W2 is not None:
-            wq2, wv2 = _mpo_entries(W2)
+            wq2, wv2 = self._table(W2)
             wl2 = list(W2.get_leg_labels())
-            ci2, co2, po2, pi2 = wl2.index(w_in), wl2.index(w_out), wl2.index(p2_out), wl2.index(p2_in)
-            xa_p2 = X.get_leg_index(x_p2)
-            assert np.all(X.legs[xa_p2].get_block_sizes() == 1)
-            i1, i2 = np.nonzero(e_out_w[:, None] == wq2[:, ci2][None, :])        # join over the common MPO bond
-            keys = np.stack([e_in_w[i1], wq2[i2, co2], e_po[i1], e_pi[i1], wq2[i2, po2], wq2[i2, pi2]], axis=1)
-            vals = e_val[i1] * np.asarray(wv2)[i2]
-            uk, inv = np.unique(keys, axis=0, return_inverse=True)
-            tot = np.zeros(len(uk), dtype=vals.dtype)
-            np.add.at(tot, inv.reshape(-1), vals)
-            keep = tot != 0
-            uk, tot = uk[keep], tot[keep]
-            e_in_w, e_out_w, e_po, e_pi, e_p2o, e_p2i, e_val = uk[:, 0], uk[:, 1], uk[:, 2], uk[:, 3], uk[:, 4], uk[:, 5], tot
-            w_leg_out = W2.get_leg(w_out)
-        xq = X._qdata
-        match = (xq[:, xa_w][:, None] == e_in_w[None, :]) & (xq[:, xa_p][:, None] == e_pi[None, :])
-        if W2 is not None:
-            match &= (xq[:, xa_p2][:, None] == e_p2i[None, :])
-        ib, ie = np.nonzero(match)
-        oq = xq[ib].copy()
-        oq[:, xa_w] = e_out_w[ie]
-        oq[:, xa_p] = e_po[ie]
-        legs = list(X.legs)
-        legs[xa_w] = w_leg_out
-        legs[xa_p] = W.get_leg(p_out)
-        labels = list(X.get_leg_labels())
-        labels[xa_w], labels[xa_p] = w_out, p_out
-        if W2 is not None:
-            oq[:, xa_p2] = e_p2o[ie]
-            legs[xa_p2] = W2.get_leg(p2_out)
-            labels[xa_p2] = p2_out
-        wv = e_val
-        perm = [labels.index(l) for l in out_labels]
+            keys2 = wq2[:, [wl2.index(l) for l in (w_in, w_out, p2_out, p2_in)]]
+            i1, i2 = np.nonzero(keys[:, 1][:, None] == keys2[:, 0][None, :])      # join over the common MPO bond
+            joined = np.stack([keys[i1, 0], keys2[i2, 1], keys[i1, 2], keys[i1, 3], keys2[i2, 2], keys2[i2, 3]], axis=1)
+            prod = vals[i1] * np.asarray(wv2)[i2]
+            uk, inv = np.unique(joined, axis=0, return_inverse=True)
+            tot = np.zeros(len(uk), dtype=prod.dtype)
+            np.add.at(tot, inv.reshape(-1), prod)
+            keys, vals = uk[tot != 0], tot[tot != 0]
+        ib, ie, oq = self._match_blocks(X, keys, xa)
+        legs, perm = self._set_output(X, W, W2, xa, w_out, p_out, p2_out, out_labels)
         big = [a for a in range(X.rank) if not np.all(legs[a].get_block_sizes() == 1)]
         assert [a for a in perm if a in big] == big, "out_labels must keep the order of the non-trivial legs"
-        oq = oq[:, perm]
-        self.legs = [legs[a] for a in perm]
-        self.labels = list(out_labels)
-        self.dtype = np.result_type(X.dtype, W.dtype) if W2 is None else np.result_type(X.dtype, W.dtype, W2.dtype)
-        self.qtotal = X.chinfo.make_valid(X.qtotal + W.qtotal + (0 if W2 is None else W2.qtotal))
         self.empty = len(ib) == 0
         if self.empty:
             return
-        uq, inv = np.unique(oq, axis=0, return_inverse=True)
-        inv = inv.reshape(-1)
-        order = np.lexsort(uq.T)
-        rank_of = np.empty(len(order), dtype=np.int64)
-        rank_of[order] = np.arange(len(order))
-        self.qdata = np.ascontiguousarray(uq[order], dtype=np.intp)
-        blk = rank_of[inv]
+        blk, sizes = self._rank_blocks(oq[:, perm])
         sizes_x = X._block_sizes_flat()
-        proto = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
-        sizes = proto._set_blocks(self.qdata, arena=dev.empty(0, self.dtype), qdata_sorted=True)
-        self.offsets = proto._offsets
-        self.total = int(np.sum(sizes))
-        key = np.lexsort((np.arange(len(blk)), blk))
-        b_sorted = blk[key]
-        first = np.concatenate([[True], b_sorted[1:] != b_sorted[:-1]])
-        starts = np.nonzero(first)[0]
-        counts = np.diff(np.concatenate([starts, [len(key)]]))
+        key, starts, counts = _group_terms(blk)
         jobs = np.zeros((len(starts), 8), dtype=np.int64)
-        sz = sizes[b_sorted[starts]]
-        jobs[:, 0], jobs[:, 1], jobs[:, 2], jobs[:, 3] = self.offsets[b_sorted[starts]], 1, sz, sz
+        sz = sizes[blk[key[starts]]]
+        jobs[:, 0], jobs[:, 1], jobs[:, 2], jobs[:, 3] = self.offsets[blk[key[starts]]], 1, sz, sz
         jobs[:, 4], jobs[:, 5] = starts, counts
         terms = np.zeros((len(key), 4), dtype=np.int64)
         terms[:, 0] = X._offsets[ib[key]]
         terms[:, 1] = sizes_x[ib[key]]
-        alpha = np.asarray(wv[ie[key]], dtype=np.complex128)
-        terms[:, 2] = np.ascontiguousarray(alpha.real).view(np.int64)
-        terms[:, 3] = np.ascontiguousarray(alpha.imag).view(np.int64)
+        _pack_alpha(terms, vals[ie[key]])
         assert len(jobs) <= 60000
         self.jobs_host, self.terms_host, self.sizes = jobs, terms, sizes      # (row-restricted copies: algorithms/sharded.py)
         self.jobs_dev, self.terms_dev = dev.to_device(jobs), dev.to_device(terms)
@@ -361,69 +436,13 @@ class MpoApplyPlan:
         self.x_key = X._struct_key()
         self.bytes = 8 * (2 if self.dtype.kind == 'c' else 1) * (self.total + int(np.sum(sizes_x[ib])))
 
-    def apply(self, X, launch=True):
-        res = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
-        if self.empty:
-            return res
-        if X.dtype != self.dtype:
-            X = X.astype(self.dtype)
-        res._set_blocks(self.qdata, arena=dev.empty(self.total, self.dtype), qdata_sorted=True)
-        if not launch:
-            return res
+    def _launch(self, X, res):
         dev.check(dev.lib().tpa_lincomb_batch(dev.code(self.dtype), self.jobs_dev.data_ptr(), self.n_jobs, self.terms_dev.data_ptr(),
                                               self.max_elems, X._arena.data_ptr(), res._arena.data_ptr(), dev.stream()), "lincomb")
-        return res
 
     def program_op(self, a_slot, c_slot):
         """The row of a ``tpa_lanczos_run`` program that applies this plan from slot ``a_slot`` into slot ``c_slot`` (kind 1)."""
         return [1, 0, self.jobs_dev.data_ptr(), self.terms_dev.data_ptr(), 0, self.n_jobs, a_slot, 0, c_slot, self.max_elems, 0, 0]
-
-
-def _mpo_blocks(W):
-    """(qdata, host copies of the stored blocks) of an MPO tensor whose two MPO bond legs have 1-wide blocks and whose physical charge
-    sectors are at most ``TPA_MPO_APPLY_MAXD`` wide, else ``None`` (cached on W like ``_tpa_entries``).  Wider bond blocks or sectors
-    go entry by entry (``_mpo_coo`` / ``MpoEntryApplyPlan``), and so do MPOs without a conserved charge -- one dense block, no charge
-    rule to select the terms -- where ``ENTRY_APPLY`` is 2; by default they keep the reference's contractions."""
-    blk = getattr(W, '_tpa_blocks', False)
-    if blk is False:
-        labels = list(W.get_leg_labels())
-        blk = None
-        if W.rank == 4 and 'wL' in labels and 'wR' in labels and W.stored_blocks > 0 and W.chinfo.qnumber > 0:
-            phys = [a for a in range(4) if labels[a] not in ('wL', 'wR')]
-            if all(np.all(W.get_leg(l).get_block_sizes() == 1) for l in ('wL', 'wR')) and \
-                    all(int(np.max(W.legs[a].get_block_sizes())) <= MPO_APPLY_MAXD for a in phys):
-                blk = (np.array(W._qdata), [np.array(b) for b in W._data])
-        W._tpa_blocks = blk
-    return blk
-
-
-def _share_mpo_tables(W_new, W):
-    """Hand the host tables cached on the MPO's own tensor ``W`` to its relabelled copy ``W_new`` (one D2H read per site and run)."""
-    W_new._tpa_entries = _mpo_entries(W)
-    if W_new._tpa_entries is None and BLOCK_APPLY and dev.lib_provides('tpa_mpo_apply_batch'):
-        W_new._tpa_blocks = _mpo_blocks(W)
-    W_new._tpa_origin = W       # (``_mpo_coo`` reads and caches its table there when a plan first asks for it)
-
-
-def _mpo_coo(W):
-    """(global indices int64[n, 4] in the stored leg order, values) of the nonzero entries of an MPO tensor with legs ``wL``, ``wR``
-    and two physical legs, whatever the widths of its blocks; ``None`` for anything else (cached on W like ``_tpa_entries``)."""
-    coo = getattr(W, '_tpa_coo', False)
-    if coo is False and getattr(W, '_tpa_origin', None) is not None:      # a relabelled copy: the table of the MPO's own tensor
-        coo = W._tpa_coo = _mpo_coo(W._tpa_origin)
-    if coo is False:
-        labels = list(W.get_leg_labels())
-        coo = None
-        if W.rank == 4 and 'wL' in labels and 'wR' in labels and W.stored_blocks > 0:
-            idx, vals = [], []
-            for q, b in zip(np.array(W._qdata).tolist(), W._data):
-                b = np.array(b)
-                nz = np.nonzero(b)
-                idx.append(np.stack([nz[a] + int(W.legs[a].slices[q[a]]) for a in range(4)], axis=1))
-                vals.append(b[nz])
-            coo = (np.concatenate(idx).astype(np.int64).reshape(-1, 4), np.concatenate(vals))
-        W._tpa_coo = coo
-    return coo
 
 
 def _entry_route(chinfo):
@@ -469,7 +488,7 @@ def _mpo_plan_class(W, W2=None):
     return MpoBlockApplyPlan
 
 
-class MpoBlockApplyPlan:
+class MpoBlockApplyPlan(_MpoStepPlan):
     """``MpoApplyPlan`` for MPO tensors whose physical charge sectors hold several states (MPO bond legs still with 1-wide blocks):
     only the 1-wide ``w`` leg changes its position, so a block of X ``(.., w, p [, p2], ..)`` is ``(pre, D_in, post)`` in memory and
     the block of Y it feeds is ``(pre, D_out, post)`` (two sites: ``D = d0 d1``) -- every block of Y is a sum of small dense matrices
@@ -477,20 +496,7 @@ class MpoBlockApplyPlan:
     ``(w_in, w_out, sectors)`` term is ``sum_w'' W[w_in, w''] (x) W2[w'', w_out]``, formed once on the host; terms whose matrix is
     exactly zero are dropped.  Arguments and attributes: see ``MpoApplyPlan``."""
     _cache = {}
-
-    @classmethod
-    def get(cls, X, W, *args, W2=None, **kwargs):
-        """Cached constructor: the plan depends on the block structure of X and on the MPO tensors only."""
-        b1, b2 = _mpo_blocks(W), (None if W2 is None else _mpo_blocks(W2))
-        key = (X._struct_key(), str(X.dtype), id(b1), None if b2 is None else id(b2), args,
-               tuple(sorted(kwargs.items())), tuple(X.get_leg_labels()))
-        plan = cls._cache.get(key)
-        if plan is None or plan._blocks_alive[0] is not b1 or plan._blocks_alive[1] is not b2:
-            if len(cls._cache) > 4096:
-                cls._cache.clear()
-            plan = cls._cache[key] = cls(X, W, *args, W2=W2, **kwargs)
-            plan._blocks_alive = (b1, b2)       # the key holds id()s: see MpoApplyPlan.get
-        return plan
+    _table = staticmethod(_mpo_blocks)
 
     @staticmethod
     def _entries(W, w_in, w_out, p_out, p_in):
@@ -503,12 +509,12 @@ class MpoBlockApplyPlan:
 
     def __init__(self, X, W, x_w, x_p, w_in, w_out, p_out, p_in, out_labels, W2=None, x_p2=None, p2_out=None, p2_in=None):
         keys, mats = self._entries(W, w_in, w_out, p_out, p_in)
-        xa_w, xa_p = X.get_leg_index(x_w), X.get_leg_index(x_p)
-        xa_p2 = None if W2 is None else X.get_leg_index(x_p2)
+        xa = [X.get_leg_index(l) for l in ((x_w, x_p) if W2 is None else (x_w, x_p, x_p2))]
+        xa_w, xa_p = xa[:2]
         assert np.all(X.legs[xa_w].get_block_sizes() == 1)
         rest = [a for a in range(X.rank) if a != xa_w]      # memory order of a block (the w leg has extent 1)
         if W2 is not None:
-            assert rest.index(xa_p2) == rest.index(xa_p) + 1, "the two physical legs must be neighbours in memory"
+            assert rest.index(xa[2]) == rest.index(xa_p) + 1, "the two physical legs must be neighbours in memory"
             keys2, mats2 = self._entries(W2, w_in, w_out, p2_out, p2_in)
             joined = {}
             for k1, m1 in zip(keys.tolist(), mats):         # join over the common MPO bond, in table order
@@ -523,87 +529,44 @@ class MpoBlockApplyPlan:
         else:
             keep = [n for n, m in enumerate(mats) if np.any(m != 0)]
             keys, mats = keys[keep], [mats[n] for n in keep]
-        self.dtype = np.result_type(X.dtype, W.dtype) if W2 is None else np.result_type(X.dtype, W.dtype, W2.dtype)
-        self.qtotal = X.chinfo.make_valid(X.qtotal + W.qtotal + (0 if W2 is None else W2.qtotal))
-        legs, labels = list(X.legs), list(X.get_leg_labels())
-        legs[xa_w], labels[xa_w] = (W if W2 is None else W2).get_leg(w_out), w_out
-        legs[xa_p], labels[xa_p] = W.get_leg(p_out), p_out
-        if W2 is not None:
-            legs[xa_p2], labels[xa_p2] = W2.get_leg(p2_out), p2_out
-        perm = [labels.index(l) for l in out_labels]
+        _, perm = self._set_output(X, W, W2, xa, w_out, p_out, p2_out, out_labels)
         assert [a for a in perm if a != xa_w] == rest, "out_labels must keep the order of the legs other than the MPO leg"
-        self.legs = [legs[a] for a in perm]
-        self.labels = list(out_labels)
-        xq = X._qdata
-        match = np.zeros((len(xq), 0), dtype=bool)
-        if len(keys):
-            match = (xq[:, xa_w][:, None] == keys[None, :, 0]) & (xq[:, xa_p][:, None] == keys[None, :, 3])
-            if W2 is not None:
-                match &= (xq[:, xa_p2][:, None] == keys[None, :, 5])
-        ib, ie = np.nonzero(match)
+        ib, ie, oq = self._match_blocks(X, keys, xa)        # (no surviving key: ``keys`` has no rows and there is no pair)
         self.empty = len(ib) == 0
         if self.empty:
             return
-        oq = xq[ib].copy()
-        oq[:, xa_w], oq[:, xa_p] = keys[ie, 1], keys[ie, 2]
-        if W2 is not None:
-            oq[:, xa_p2] = keys[ie, 4]
-        oq = oq[:, perm]
-        uq, inv = np.unique(oq, axis=0, return_inverse=True)
-        inv = inv.reshape(-1)
-        order = np.lexsort(uq.T)
-        rank_of = np.empty(len(order), dtype=np.int64)
-        rank_of[order] = np.arange(len(order))
-        self.qdata = np.ascontiguousarray(uq[order], dtype=np.intp)
-        blk = rank_of[inv]
-        proto = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
-        sizes = proto._set_blocks(self.qdata, arena=dev.empty(0, self.dtype), qdata_sorted=True)
-        self.offsets = proto._offsets
-        self.total = int(np.sum(sizes))
+        blk, sizes = self._rank_blocks(oq[:, perm])
         # coefficient table: the matrices back to back, row-major (d_out, d_in)
         m_shape = np.array([m.shape for m in mats], dtype=np.int64)
         m_off = np.concatenate([[0], np.cumsum(m_shape[:, 0] * m_shape[:, 1])])
         coeff = np.concatenate([np.asarray(m, dtype=self.dtype).reshape(-1) for m in mats])
         shapes_x, sizes_x = X._block_shapes(), X._block_sizes_flat()
         lead = rest[:rest.index(xa_p)]
-        pre = np.prod(shapes_x[:, lead], axis=1) if lead else np.ones(len(xq), dtype=np.int64)
+        pre = np.prod(shapes_x[:, lead], axis=1) if lead else np.ones(len(shapes_x), dtype=np.int64)
         d_in = m_shape[:, 1]
-        post = sizes_x // (pre * shapes_x[:, xa_p] * (1 if W2 is None else shapes_x[:, xa_p2]))
+        post = sizes_x // (pre * shapes_x[:, xa_p] * (1 if W2 is None else shapes_x[:, xa[2]]))
         assert np.array_equal(pre[ib] * d_in[ie] * post[ib], sizes_x[ib])
-        key = np.lexsort((np.arange(len(blk)), blk))        # one job per block of Y, its terms in a fixed order
-        b_sorted = blk[key]
-        first = np.concatenate([[True], b_sorted[1:] != b_sorted[:-1]])
-        starts = np.nonzero(first)[0]
-        counts = np.diff(np.concatenate([starts, [len(key)]]))
+        key, starts, counts = _group_terms(blk)             # one job per block of Y, its terms in a fixed order
         kf = key[starts]
         jobs = np.zeros((len(starts), 8), dtype=np.int64)
-        jobs[:, 0], jobs[:, 1], jobs[:, 2], jobs[:, 3] = self.offsets[b_sorted[starts]], pre[ib[kf]], m_shape[ie[kf], 0], post[ib[kf]]
+        jobs[:, 0], jobs[:, 1], jobs[:, 2], jobs[:, 3] = self.offsets[blk[kf]], pre[ib[kf]], m_shape[ie[kf], 0], post[ib[kf]]
         jobs[:, 4], jobs[:, 5] = starts, counts
-        assert np.array_equal(jobs[:, 1] * jobs[:, 2] * jobs[:, 3], sizes[b_sorted[starts]])
+        assert np.array_equal(jobs[:, 1] * jobs[:, 2] * jobs[:, 3], sizes[blk[kf]])
         terms = np.zeros((len(key), 4), dtype=np.int64)
         terms[:, 0], terms[:, 1], terms[:, 2] = X._offsets[ib[key]], d_in[ie[key]], m_off[ie[key]]
         assert len(jobs) <= 60000
         self.jobs_host, self.terms_host, self.coeff_host, self.sizes = jobs, terms, coeff, sizes
         self.jobs_dev, self.terms_dev, self.coeff_dev = dev.to_device(jobs), dev.to_device(terms), dev.to_device(coeff)
-        self.n_jobs, self.max_elems = len(jobs), int(np.max(sizes[b_sorted[starts]]))
+        self.n_jobs, self.max_elems = len(jobs), int(np.max(sizes[blk[kf]]))
         self.max_d = int(max(np.max(jobs[:, 2]), np.max(terms[:, 1])))
         assert self.max_d <= MPO_APPLY_MAXD
         self.x_key = X._struct_key()
         self.bytes = 8 * (2 if self.dtype.kind == 'c' else 1) * (self.total + int(np.sum(sizes_x[ib])))
 
-    def apply(self, X, launch=True):
-        res = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
-        if self.empty:
-            return res
-        if X.dtype != self.dtype:
-            X = X.astype(self.dtype)
-        res._set_blocks(self.qdata, arena=dev.empty(self.total, self.dtype), qdata_sorted=True)
-        if not launch:
-            return res
+    def _launch(self, X, res):
         dev.check(dev.lib().tpa_mpo_apply_batch(dev.code(self.dtype), self.jobs_dev.data_ptr(), self.n_jobs, self.terms_dev.data_ptr(),
                                                 self.coeff_dev.data_ptr(), self.max_d, self.max_elems, X._arena.data_ptr(),
                                                 res._arena.data_ptr(), dev.stream()), "mpo_apply")
-        return res
 
     def program_op(self, a_slot, c_slot):
         """The row of a ``tpa_lanczos_run`` program that applies this plan from slot ``a_slot`` into slot ``c_slot`` (kind 5)."""
@@ -618,7 +581,7 @@ def _leg_block_pos(leg, idx):
     return b, idx - sl[b]
 
 
-class MpoEntryApplyPlan:
+class MpoEntryApplyPlan(_MpoStepPlan):
     """``MpoApplyPlan`` for MPO tensors of any block structure -- MPO bond legs with blocks wider than 1, physical sectors wider than
     ``TPA_MPO_APPLY_MAXD``, no conserved charge -- entry by entry.  X has its two virtual legs first and last and the MPO and physical
     legs between them, so a block of X is ``(pre, M_in, post)`` in memory and the block of Y it feeds is ``(pre, M_out, post)`` with the
@@ -628,20 +591,7 @@ class MpoEntryApplyPlan:
     or -- calls with few blocks -- per range of its rows.  Arguments and attributes: see ``MpoApplyPlan``."""
     _cache = {}
     SPLIT_BELOW = 512       # calls with fewer blocks of Y than this split the rows of a block over several jobs
-
-    @classmethod
-    def get(cls, X, W, *args, W2=None, **kwargs):
-        """Cached constructor: the plan depends on the block structure of X and on the MPO tensors only."""
-        c1, c2 = _mpo_coo(W), (None if W2 is None else _mpo_coo(W2))
-        key = (X._struct_key(), str(X.dtype), id(c1), None if c2 is None else id(c2), args,
-               tuple(sorted(kwargs.items())), tuple(X.get_leg_labels()))
-        plan = cls._cache.get(key)
-        if plan is None or plan._coo_alive[0] is not c1 or plan._coo_alive[1] is not c2:
-            if len(cls._cache) > 4096:
-                cls._cache.clear()
-            plan = cls._cache[key] = cls(X, W, *args, W2=W2, **kwargs)
-            plan._coo_alive = (c1, c2)          # the key holds id()s: see MpoApplyPlan.get
-        return plan
+    _table = staticmethod(_mpo_coo)
 
     @staticmethod
     def _entries(W, w_in, w_out, p_out, p_in):
@@ -664,19 +614,10 @@ class MpoEntryApplyPlan:
             np.add.at(tot, inv.reshape(-1), vals[i1] * vals2[i2])
             keep = tot != 0
             keys, vals = uk[keep], tot[keep]
-        self.dtype = np.result_type(X.dtype, W.dtype) if W2 is None else np.result_type(X.dtype, W.dtype, W2.dtype)
-        self.qtotal = X.chinfo.make_valid(X.qtotal + W.qtotal + (0 if W2 is None else W2.qtotal))
-        xa = [X.get_leg_index(x_w), X.get_leg_index(x_p)] + ([] if W2 is None else [X.get_leg_index(x_p2)])
-        legs, labels = list(X.legs), list(X.get_leg_labels())
-        legs[xa[0]], labels[xa[0]] = (W if W2 is None else W2).get_leg(w_out), w_out
-        legs[xa[1]], labels[xa[1]] = W.get_leg(p_out), p_out
-        if W2 is not None:
-            legs[xa[2]], labels[xa[2]] = W2.get_leg(p2_out), p2_out
-        perm = [labels.index(l) for l in out_labels]
+        xa = [X.get_leg_index(l) for l in ((x_w, x_p) if W2 is None else (x_w, x_p, x_p2))]
+        legs, perm = self._set_output(X, W, W2, xa, w_out, p_out, p2_out, out_labels)
         mid = list(range(1, X.rank - 1))
         assert sorted(xa) == mid and perm[0] == 0 and perm[-1] == X.rank - 1, "X: virtual legs first and last, the MPO step between them"
-        self.legs = [legs[a] for a in perm]
-        self.labels = list(out_labels)
         # (block, position) of every entry on the legs of X (in) and of Y (out); columns of `keys`: w_in, w_out, p_out, p_in [, p2_out, p2_in]
         col_in, col_out = [0, 3, 5], [1, 2, 4]
         b_in, pos_in, b_out, pos_out = {}, {}, {}, {}
@@ -700,18 +641,7 @@ class MpoEntryApplyPlan:
         oq = xq[ib].copy()
         for a in mid:
             oq[:, a] = b_out[a][ie]
-        oq = oq[:, perm]
-        uq, inv = np.unique(oq, axis=0, return_inverse=True)
-        inv = inv.reshape(-1)
-        order = np.lexsort(uq.T)
-        rank_of = np.empty(len(order), dtype=np.int64)
-        rank_of[order] = np.arange(len(order))
-        self.qdata = np.ascontiguousarray(uq[order], dtype=np.intp)
-        blk = rank_of[inv]
-        proto = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
-        sizes = proto._set_blocks(self.qdata, arena=dev.empty(0, self.dtype), qdata_sorted=True)
-        self.offsets = proto._offsets
-        self.total = int(np.sum(sizes))
+        blk, sizes = self._rank_blocks(oq[:, perm])
         # middle row of the source (order of X's legs) and of the destination (order of out_labels) of every pair
         shapes_x, sizes_x = X._block_shapes(), X._block_sizes_flat()
         c = np.zeros(len(ib), dtype=np.int64)
@@ -738,9 +668,7 @@ class MpoEntryApplyPlan:
         terms = np.zeros((len(key), 4), dtype=np.int64)
         terms[:, 0] = X._offsets[ib[key]] + c[key] * post_x[key]
         terms[:, 1] = m_in[key] * post_x[key]
-        alpha = np.asarray(vals[ie[key]], dtype=np.complex128)
-        terms[:, 2] = np.ascontiguousarray(alpha.real).view(np.int64)
-        terms[:, 3] = np.ascontiguousarray(alpha.imag).view(np.int64)
+        _pack_alpha(terms, vals[ie[key]])
         # jobs: one per block of Y; with few blocks the rows of a block are split over several jobs (dst_ld = the whole block's rows)
         pieces = 1 if len(sizes) >= self.SPLIT_BELOW else -(-self.SPLIT_BELOW // len(sizes))
         per_job = np.maximum(1, -(-m_out // pieces))
@@ -757,19 +685,10 @@ class MpoEntryApplyPlan:
         self.x_key = X._struct_key()
         self.bytes = 8 * (2 if self.dtype.kind == 'c' else 1) * (self.total + int(np.sum(shapes_x[ib, 0] * post_x)))
 
-    def apply(self, X, launch=True):
-        res = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
-        if self.empty:
-            return res
-        if X.dtype != self.dtype:
-            X = X.astype(self.dtype)
-        res._set_blocks(self.qdata, arena=dev.empty(self.total, self.dtype), qdata_sorted=True)
-        if not launch:
-            return res
+    def _launch(self, X, res):
         dev.check(dev.lib().tpa_mpo_entry_apply_batch(dev.code(self.dtype), self.jobs_dev.data_ptr(), self.n_jobs, self.rows_dev.data_ptr(),
                                                       self.terms_dev.data_ptr(), self.max_cols, X._arena.data_ptr(), res._arena.data_ptr(),
                                                       dev.stream()), "mpo_entry_apply")
-        return res
 
     def program_op(self, a_slot, c_slot):
         """The row of a ``tpa_lanczos_run`` program that applies this plan from slot ``a_slot`` into slot ``c_slot`` (kind 6)."""
@@ -837,6 +756,56 @@ def _gemm_ops(plan, a_slot, b_slot, c_slot, bufs, scratch_name):
     part = len(bufs) - 1
     return [[0, plan.cfg, sk.tasks_dev.data_ptr(), sk.links_dev.data_ptr(), sk.tiles_dev.data_ptr(), sk.n_tiles, a_slot, b_slot, part, 0, 0, 0],
             [1, 1, sk.jobs_dev.data_ptr(), sk.terms_dev.data_ptr(), 0, sk.n_jobs, part, 0, c_slot, sk.max_elems, 0, 0]]
+
+
+# The labels of an MPO step -- x_w, x_p, w_in, w_out, p_out, p_in of ``MpoApplyPlan`` -- going left to right (W0 on the legs wR, p0 of
+# X = LP . theta, wL -> wR) and going right to left (W1 on the legs wL, p1 of X = theta . RP, wR -> wL: ``update_RP``, the right mixer).
+_STEP_LR = ('wR', 'p0', 'wL', 'wR', 'p0', 'p0*')
+_STEP_RL = ('wL', 'p1', 'wR', 'wL', 'p1', 'p1*')
+
+
+def _mpo_step_lr(X, W0, W1=None, *, out_labels):
+    """The cached plan (``_mpo_plan_class``) that applies W0 -- with ``W1``: W0 W1 on the legs wR, p0, p1 in ONE pass -- to X from left
+    to right, giving Y with the legs ``out_labels``."""
+    two = {} if W1 is None else dict(W2=W1, x_p2='p1', p2_out='p1', p2_in='p1*')
+    return _mpo_plan_class(W0, W1).get(X, W0, *_STEP_LR, tuple(out_labels), **two)
+
+
+def _mpo_step_rl(X, W1, *, out_labels):
+    """The cached plan that applies W1 to X from right to left."""
+    return _mpo_plan_class(W1).get(X, W1, *_STEP_RL, tuple(out_labels))
+
+
+def _factored_plans(LPf, RPf, theta, W0, W1=None, launch=False, old=None):
+    """The plans of the factored forms as the dict that an operator keeps in ``_fplans`` and the drivers hand from visit to visit of a
+    bond: ``p1`` (``LPf . theta``, GEMM), the MPO step (``a01`` for W0 W1, ``a0`` for W0 alone, ``None`` without a site), ``p2``
+    (``. RPf``, GEMM chained over wR and the bond sector) and what they were made for: the structure keys ``key`` (theta), ``lkey``,
+    ``rkey`` and ``dtype``.  Returns ``(plans, T1, T)``: ``old`` itself and no tensors if it was made for the same structures (the
+    environments grow between visits), else new plans with the results of step 1 and of the MPO step.  ``launch``: these two steps
+    run while the plans are built (``plans['p2'].apply(T, RPf)`` completes the matvec), a step that needs a transposed copy is an
+    assertion failure and an empty step gives empty plans.  Without it nothing is launched (T1, T: block structure only), and a
+    transposed copy or an empty step means that there are no plans: ``(None, None, None)``."""
+    keys = dict(key=theta._struct_key(), dtype=theta.dtype, lkey=LPf._struct_key(), rkey=RPf._struct_key())
+    if old is not None and all(old[k] == v for k, v in keys.items()):
+        return old, None, None
+    p1, l_use, t_use = npc.plan_tensordot(LPf, theta, axes=['vR', 'vL'])
+    fits = l_use is LPf and t_use is theta
+    assert fits or not launch, "factored matvec step 1 must not need a transpose"
+    if not fits or (p1.empty and not launch):
+        return None, None, None
+    T = T1 = p1.apply(LPf, theta, launch=launch)                   # vR*, wR, [p0, [p1,]] vR
+    a = None
+    if W0 is not None:
+        a = _mpo_step_lr(T1, W0, W1, out_labels=('vR*', 'p0', 'wR', 'vR') if W1 is None else ('vR*', 'p0', 'p1', 'wR', 'vR'))
+        if a.empty and not launch:
+            return None, None, None
+        T = a.apply(T1, launch=launch)                             # vR*, p0, [p1,] wR, vR
+    p2, t_use, r_use = npc.plan_tensordot(T, RPf, axes=(['wR', 'vR'], ['wL', 'vL']))
+    fits = t_use is T and r_use is RPf
+    assert fits or not launch, "factored matvec step 2 must not need a transpose"
+    if not fits or (p2.empty and not launch):
+        return None, None, None
+    return dict(keys, p1=p1, p2=p2, **{'a0' if W1 is None else 'a01': a}), T1, T
 
 
 class _DeviceEffectiveH:
@@ -1015,31 +984,25 @@ class TwoSiteH(_DeviceEffectiveH):
         """theta [vL, p0, p1, vR] -> LP . theta . W0 W1 . RP with the same legs:
         T1 = LP . theta (GEMM, contracted index = chi, not d chi);  T3 = MPO tensors applied blockwise (lincomb);
         theta' = T3 . RP (GEMM, chain over wR and the bond sector)."""
-        fp = self._fplans
-        if fp is not None and (fp['lkey'] != self._LPf._struct_key() or fp['rkey'] != self._RPf._struct_key()):
-            fp = None               # plans handed over from an earlier visit of the bond: the environments changed shape since
-        if fp is None or fp['key'] != theta._struct_key() or fp['dtype'] != theta.dtype:
-            p1, l_use, t_use = npc.plan_tensordot(self._LPf, theta, axes=['vR', 'vL'])
-            assert l_use is self._LPf and t_use is theta, "factored matvec step 1 must not need a transpose"
-            T1 = p1.apply(self._LPf, theta)                                    # vR*, wR, p0, p1, vR
-            a01 = _mpo_plan_class(self.W0, self.W1).get(T1, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'p1', 'wR', 'vR'),
-                                                        W2=self.W1, x_p2='p1', p2_out='p1', p2_in='p1*')   # both MPO tensors in ONE pass
-            T3 = a01.apply(T1)
-            p2, t3_use, r_use = npc.plan_tensordot(T3, self._RPf, axes=(['wR', 'vR'], ['wL', 'vL']))
-            assert t3_use is T3 and r_use is self._RPf, "factored matvec step 2 must not need a transpose"
-            self._fplans = dict(key=theta._struct_key(), dtype=theta.dtype, p1=p1, a01=a01, p2=p2,
-                                lkey=self._LPf._struct_key(), rkey=self._RPf._struct_key())
-            if not p1.empty and not p2.empty:
-                self.flops_per_matvec = p1.flops + p2.flops
-                self.bytes_per_matvec = p1.bytes_min + p2.bytes_min + a01.bytes
-                self.gemm_shapes = (p1.gemm_shapes, p2.gemm_shapes)
-            res = p2.apply(T3, self._RPf)
-        else:
-            T1 = fp['p1'].apply(self._LPf, theta)
-            T3 = fp['a01'].apply(T1)
-            res = fp['p2'].apply(T3, self._RPf)
+        fp, T3 = self._plans_for(theta, launch=True)
+        if T3 is None:              # plans that were there already; building them runs the first two steps
+            T3 = fp['a01'].apply(fp['p1'].apply(self._LPf, theta))
+        res = fp['p2'].apply(T3, self._RPf)
         res.iset_leg_labels(['vL', 'p0', 'p1', 'vR'])
         return res
+
+    def _plans_for(self, theta, launch):
+        """``_factored_plans`` for ``theta``: the plans (``None``: there are none, and ``_fplans`` stays) and the result of the MPO
+        step if they were built now; new plans are kept in ``_fplans`` with their flop and byte counts."""
+        fp, _, T3 = _factored_plans(self._LPf, self._RPf, theta, self.W0, self.W1, launch, old=self._fplans)
+        if fp is not None and fp is not self._fplans:
+            self._fplans = fp
+            p1, p2 = fp['p1'], fp['p2']
+            if not p1.empty and not p2.empty:
+                self.flops_per_matvec = p1.flops + p2.flops
+                self.bytes_per_matvec = p1.bytes_min + p2.bytes_min + fp['a01'].bytes
+                self.gemm_shapes = (p1.gemm_shapes, p2.gemm_shapes)
+        return fp, T3
 
     def matvec(self, theta):
         """theta [(vL.p0), (p1.vR)] (fused mode) or [vL, p0, p1, vR] (factored mode) -> H_eff theta, same legs and labels."""
@@ -1082,27 +1045,9 @@ class TwoSiteH(_DeviceEffectiveH):
             return prog[1]
         res = None
         if self.factored:
-            fp = self._fplans
-            if fp is not None and (fp['lkey'] != self._LPf._struct_key() or fp['rkey'] != self._RPf._struct_key()):
-                fp = None           # (plans handed over from the previous visit of this bond, `plan_cache`: the environments changed shape)
-            if fp is None or fp['key'] != theta._struct_key() or fp['dtype'] != theta.dtype:
-                p1, l_use, t_use = npc.plan_tensordot(self._LPf, theta, axes=['vR', 'vL'])
-                if l_use is not self._LPf or t_use is not theta or p1.empty:
-                    return None
-                T1 = p1.apply(self._LPf, theta, launch=False)
-                a01 = _mpo_plan_class(self.W0, self.W1).get(T1, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'p1', 'wR', 'vR'),
-                                                            W2=self.W1, x_p2='p1', p2_out='p1', p2_in='p1*')
-                if a01.empty:
-                    return None
-                T3 = a01.apply(T1, launch=False)
-                p2, t3_use, r_use = npc.plan_tensordot(T3, self._RPf, axes=(['wR', 'vR'], ['wL', 'vL']))
-                if t3_use is not T3 or r_use is not self._RPf or p2.empty:
-                    return None
-                self._fplans = fp = dict(key=theta._struct_key(), dtype=theta.dtype, p1=p1, a01=a01, p2=p2,
-                                         lkey=self._LPf._struct_key(), rkey=self._RPf._struct_key())
-                self.flops_per_matvec = p1.flops + p2.flops
-                self.bytes_per_matvec = p1.bytes_min + p2.bytes_min + a01.bytes
-                self.gemm_shapes = (p1.gemm_shapes, p2.gemm_shapes)
+            fp = self._plans_for(theta, launch=False)[0]
+            if fp is None:
+                return None
             p1, a01, p2 = fp['p1'], fp['a01'], fp['p2']
             ok = (p1.dtype == a01.dtype == p2.dtype == theta.dtype == self._LPf.dtype == self._RPf.dtype and not p1.empty and
                   not p2.empty and not a01.empty)
@@ -1145,7 +1090,7 @@ class TwoSiteH(_DeviceEffectiveH):
             A = U.split_legs(['(vL.p0)'])                                        # vL, p0, vR
             cls = _mpo_plan_class(self.W0)
             X = npc.tensordot(self._LPf if cls is MpoEntryApplyPlan else self.LP, A, axes=['vR', 'vL'])     # vR*, wR, p0, vR
-            X = cls.get(X, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'wR', 'vR')).apply(X)
+            X = _mpo_step_lr(X, self.W0, out_labels=('vR*', 'p0', 'wR', 'vR')).apply(X)
             LP = npc.tensordot(A.conj(), X, axes=(['vL*', 'p0*'], ['vR*', 'p0']))   # vR*, wR, vR
             LP = _env_form(LP, list(self.LP.get_leg_labels()))
             _env_set_LP(env, i, LP)
@@ -1162,7 +1107,7 @@ class TwoSiteH(_DeviceEffectiveH):
             B = VH.split_legs(['(p1.vR)'])                                       # vL, p1, vR
             cls = _mpo_plan_class(self.W1)
             X = npc.tensordot(B, self._RPf if cls is MpoEntryApplyPlan else self.RP, axes=['vR', 'vL'])     # vL, p1, wL, vL*
-            X = cls.get(X, self.W1, 'wL', 'p1', 'wR', 'wL', 'p1', 'p1*', ('vL', 'wL', 'p1', 'vL*')).apply(X)
+            X = _mpo_step_rl(X, self.W1, out_labels=('vL', 'wL', 'p1', 'vL*')).apply(X)
             RP = npc.tensordot(X, B.conj(), axes=(['p1', 'vL*'], ['p1*', 'vR*']))   # vL, wL, vL*
             RP = _env_form(RP, list(self.RP.get_leg_labels()))
             _env_set_RP(env, i, RP)
@@ -1233,26 +1178,8 @@ class _LocalH(_DeviceEffectiveH):
         """The cached plans of the three (two) steps for this ``theta`` -- rebuilt whenever the block structure of ``theta`` OR of an
         environment differs from the one they were made for (plans are handed from visit to visit of a site while the
         environments grow); ``None`` when a step would need a transposed copy or contributes nothing."""
-        fp = self._fplans
-        tkey, lkey, rkey = theta._struct_key(), self._LPf._struct_key(), self._RPf._struct_key()
-        if fp is not None and fp['key'] == tkey and fp['dtype'] == theta.dtype and fp['lkey'] == lkey and fp['rkey'] == rkey:
-            return fp
-        self._fplans = None
-        p1, l_use, t_use = npc.plan_tensordot(self._LPf, theta, axes=['vR', 'vL'])
-        if l_use is not self._LPf or t_use is not theta or p1.empty:
-            return None
-        T = p1.apply(self._LPf, theta, launch=False)               # vR*, wR, [p0,] vR
-        a0 = None
-        if self.W0 is not None:
-            a0 = _mpo_plan_class(self.W0).get(T, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'wR', 'vR'))
-            if a0.empty:
-                return None
-            T = a0.apply(T, launch=False)                          # vR*, p0, wR, vR
-        p2, t_use, r_use = npc.plan_tensordot(T, self._RPf, axes=(['wR', 'vR'], ['wL', 'vL']))
-        if t_use is not T or r_use is not self._RPf or p2.empty:
-            return None
-        self._fplans = fp = dict(key=tkey, dtype=theta.dtype, lkey=lkey, rkey=rkey, p1=p1, a0=a0, p2=p2)
-        return fp
+        self._fplans = _factored_plans(self._LPf, self._RPf, theta, self.W0, old=self._fplans)[0]
+        return self._fplans
 
     def matvec(self, theta):
         """``theta`` with the labels of ``acts_on`` (any order) -> ``H_eff theta``, same legs and labels."""

@@ -182,19 +182,12 @@ class ShardedTwoSiteH(TwoSiteH):
 
     # ---- factored operator: LP[rows] . theta -> (W0 W1) blockwise on the panel rows -> T3[rows] . RP ---------------
     def _build_sharded_factored(self, theta):
-        from .mps_common import MpoApplyPlan
-        p1, _, _ = npc.plan_tensordot(self._LPf, theta, axes=['vR', 'vL'])
-        if p1.empty:
+        from .mps_common import MpoApplyPlan, _factored_plans
+        fp, T1, T3 = _factored_plans(self._LPf, self._RPf, theta, self.W0, self.W1)     # (T1, T3: their block structure is what is kept)
+        if fp is None:
             return None
-        T1 = p1.apply(self._LPf, theta)                     # full product once per bond: fixes the block structure
-        a01 = MpoApplyPlan.get(T1, self.W0, 'wR', 'p0', 'wL', 'wR', 'p0', 'p0*', ('vR*', 'p0', 'p1', 'wR', 'vR'),
-                               W2=self.W1, x_p2='p1', p2_out='p1', p2_in='p1*')
-        if a01.empty:
-            return None
-        T3 = a01.apply(T1)
-        p2, _, _ = npc.plan_tensordot(T3, self._RPf, axes=(['wR', 'vR'], ['wL', 'vL']))
-        if p2.empty:
-            return None
+        p1, a01, p2 = fp['p1'], fp['a01'], fp['p2']
+        assert type(a01) is MpoApplyPlan, "the row-restricted tables below are those of MpoApplyPlan"
         leg0 = self._LPf.legs[0]
         weights = np.zeros(leg0.ind_len)
         for plan in (p1, p2):
