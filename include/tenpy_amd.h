@@ -67,6 +67,29 @@ const char *tpa_last_error(void);
 int tpa_gemm_chain(int dtype, int cfg, const int64_t *tasks_dev, const int64_t *links_dev,
                    const int32_t *tiles_dev, int n_tiles, const void *Abase, const void *Bbase,
                    void *Cbase, void *stream);
+/* The same launch with EXTENDED LINKS (TPA_F64 only; TPA_E_BADARG for another dtype or when A2base or alphas_dev is NULL).  Tables as
+ * above, and in link.flags:
+ *   bit 2       second source: A_l is read from A2base instead of Abase (a chain may mix both);
+ *   bits 16-31  scale: index i into alphas_dev, an array of (re, im) PAIRS of doubles (real data uses the first of a pair); i = 0 means
+ *               no scale.  Every element of A_l is multiplied by alphas[2 i] on its way into LDS -- one rounding, the single-term
+ *               product of tpa_lincomb_batch: a scaled link gives bit for bit what tpa_gemm_chain gives on a copy of the block
+ *               that tpa_lincomb_batch scaled.  A chain without an extended link gives the bits of tpa_gemm_chain;
+ *   bit 3       unit factor: B_l is the unit matrix and the link adds alpha * A_l(row, col) to C_t(row, col), read from global memory
+ *               in the epilogue with the strides a_rs (row) and a_ks (column); A_l is m x n.  Store such links with k = 0.  Their
+ *               terms are added to the sum of the products in chain order, before `accumulate`; a chain may consist of them alone.
+ * A2base and alphas_dev are read only by links that ask for them. */
+int tpa_gemm_chain_ex(int dtype, int cfg, const int64_t *tasks_dev, const int64_t *links_dev, const int32_t *tiles_dev, int n_tiles,
+                      const void *Abase, const void *A2base, const void *Bbase, void *Cbase, const double *alphas_dev, void *stream);
+
+/* Which of the two loops a launch of n_tiles tiles runs on: 0 = gemm_chain_kernel, 1 = gemm_chain2_kernel (host only; follows
+ * tpa_gemm_set_variant).  Both give their own bits: a caller that drops tiles from a launch and wants the bits of the full launch keeps
+ * the answer the same. */
+int tpa_gemm_kernel_id(int dtype, int cfg, int n_tiles);
+
+/* Largest |B(i, j) - delta_ij| over a list of square blocks, exact (a maximum, no sums): jobs int64[n_jobs][4] = {offset, n, row
+ * stride, 0} in elements of `dtype` relative to src_base (DEVICE table).  out_dev[0] (one DEVICE double) receives the result, 0 for an
+ * empty list, +inf if an entry is NaN.  Asynchronous on `stream`.  n_jobs <= 65535. */
+int tpa_unit_defect_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const void *src_base, double *out_dev, void *stream);
 
 /* ---- K1h: grouped, chained, weighted Hermitian rank-k update  (the contraction in the middle of
  *          DensityMatrixMixer.mix_rho, mps_common.py:2002-2026: rho = X diag(mix) X^dagger per charge sector, which the
@@ -179,6 +202,8 @@ int tpa_project_out(int dtype, int64_t n, const void *basis_dev, int m, int64_t 
  *         kind 6: {6, 0, jobs, rows, terms, n_jobs, a_slot, 0, c_slot, max_cols, 0, 0} -- tpa_mpo_entry_apply_batch(dtype, jobs = p0,
  *                 n_jobs = count, rows = p1, terms = p2, max_job_cols = max_elems, src = A, dst = C): the MPO step of a factored operator
  *                 whose MPO index sits inside the blocks (wide MPO bond blocks, wide sectors).  Not counted as GEMM time.
+ *         kind 7: {7, cfg, tasks, links, tiles, n_tiles, a_slot, b_slot, c_slot, a2_slot, alphas, 0} -- kind 0 through
+ *                 tpa_gemm_chain_ex: A2 = the slot in field 9, alphas_dev = the device pointer in field 10.  Counted as GEMM time.
  *         slots: >= 0 -> bufs[slot] (HOST array of n_bufs device pointers: fixed operands and temporaries), -1 -> the input
  *         vector v_k, -2 -> the output vector w of this matvec.  (p0..p2 are device pointers stored as integers.)
  *   krylov_dev : (N_max + 1) * n elements; on return vectors 0 .. N-1 are the orthonormal Krylov basis (v_0 = psi0 / |psi0|).

@@ -31,6 +31,9 @@ _SIGS = {
     "tpa_gemm_tile_shape": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "tpa_gemm_set_variant": (ctypes.c_int, [ctypes.c_int]),
     "tpa_gemm_chain": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "tpa_gemm_chain_ex": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tpa_gemm_kernel_id": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "tpa_unit_defect_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp]),
     "tpa_herk_tile_shape": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]),
     "tpa_herk_chain": (ctypes.c_int, [ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "tpa_axpy": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp]),

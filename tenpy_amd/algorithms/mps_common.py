@@ -44,6 +44,10 @@ from .._lib import MPO_APPLY_MAXD      # noqa: E402  (TPA_MPO_APPLY_MAXD)
 # default: tests/test_onesite_heff.py::test_generic_route_without_charges states the reference's contractions as the route of a
 # charge-free MPO on both backends, and nothing has been measured that would justify moving it.
 ENTRY_APPLY = int(_os.environ.get('TPA_MPO_ENTRY_APPLY', '1'))
+# The launch program of the factored two-site matvec without the work nobody reads (``TwoSiteH._skip_program``): blocks of
+# T1 that no term of the MPO step reads are not computed, and a block of T3 that is one term ``alpha . block of T1`` is read from T1 by
+# a scaled link of ``tpa_gemm_chain_ex`` instead of being written and read back.  The bits of the full program.  A/B knob: '0' = off.
+MATVEC_SKIP = _os.environ.get('TPA_MATVEC_UNIT', '1') != '0'
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Fused construction of LHeff / RHeff:  LP.W0 (resp. W1.RP) + combine_legs in ONE kernel launch.
@@ -166,6 +170,7 @@ def _group_terms(dst):
 
 from collections import OrderedDict as _OrderedDict
 _heff_plans = _OrderedDict()
+_skip_table_cache = _OrderedDict()      # ids of the three plans -> (the plans, tables of `TwoSiteH._skip_program`)
 
 
 def _fused_heff(env_t, W, left):
@@ -874,6 +879,9 @@ class TwoSiteH(_DeviceEffectiveH):
         _share_mpo_tables(self.W0, W0)
         _share_mpo_tables(self.W1, W1)
         self._env = env         # (with explicit tensors: None, or the holder of the caches of `plus_hc`)
+        # `_skip_program` serves the operators the drivers build from an environment (explicit tensors, a half MPO with
+        # `explicit_plus_hc` whose operator runs as `PlusHcH`, the sharded subclass: the full program)
+        self._skip_ok = tensors is None and not getattr(env.H, 'explicit_plus_hc', False)
         self._LHeff = self._RHeff = None
         self._plans = None
         self._fplans = None
@@ -1052,6 +1060,9 @@ class TwoSiteH(_DeviceEffectiveH):
             ok = (p1.dtype == a01.dtype == p2.dtype == theta.dtype == self._LPf.dtype == self._RPf.dtype and not p1.empty and
                   not p2.empty and not a01.empty)
             if ok:
+                res = self._skip_program(theta, fp)
+                last = p2
+            if ok and res is None:
                 bufs = [self._LPf._arena, self._RPf._arena, dev.scratch('lanczos_t1', p1.res_total, p1.dtype),
                         dev.scratch('lanczos_t3', a01.total, a01.dtype)]
                 ops = _gemm_ops(p1, 0, -1, 2, bufs, 'lanczos_sk1')
@@ -1082,6 +1093,154 @@ class TwoSiteH(_DeviceEffectiveH):
 
     def _plan_matches(self, theta):
         return self._plans[2] == theta._struct_key() and self._plans[3] == theta.dtype
+
+    # ---- the launch program without the work nobody reads ----------------------------------------------------
+    def _skip_program(self, theta, fp):
+        """The program of the factored matvec with the bits of the full program and less work, or ``None`` (the caller then builds the
+        full program):
+
+        a (kind 0)  step 1 with the tiles of the blocks of T1 that some term of the MPO step reads (split-K as ``p1`` has it, with the
+                    reduction jobs of these blocks).  All tiles stay where dropping some would move the launch to another kernel
+                    (``tpa_gemm_kernel_id``);
+        b (kind 1)  the MPO step for the blocks of T3 that have several terms;
+        c (kind 7)  step 2 through ``tpa_gemm_chain_ex`` on the tables of ``p2`` (split-K: of its parts, then their reduction as today),
+                    in which a link over a block of T3 that is ONE term ``alpha . block of T1`` reads that block of T1 as the second
+                    source and scales it on its way into LDS -- the rounding of ``tpa_lincomb_batch``.
+
+        Same chains, same order, same tile tables.  For operators of this very class built from an environment, float64,
+        ``MpoApplyPlan``, a closed block structure and a library that provides ``tpa_gemm_chain_ex``.  Tables per block structure:
+        ``_skip_table_cache``.  Counters: ``krylov_based.stats['n_skip_taken' / 'n_skip_declined']``, reasons in
+        ``krylov_based.skip_declined``."""
+        from ..linalg import krylov_based as kb
+        p1, a01, p2 = fp['p1'], fp['a01'], fp['p2']
+        if not MATVEC_SKIP or not (p2.res_total == theta._arena.numel() and np.array_equal(p2.res_qdata, theta._qdata) and
+                                   np.array_equal(p2.res_offsets, theta._offsets)):
+            return None                     # (switched off; H creates blocks: `_file_program` keeps no program either way)
+
+        def declined(reason):
+            kb.stats['n_skip_declined'] += 1
+            kb.skip_declined[reason] = kb.skip_declined.get(reason, 0) + 1
+            return None
+        if type(self) is not TwoSiteH or not self._skip_ok:
+            return declined('operator')
+        if type(a01) is not MpoApplyPlan:
+            return declined('mpo_plan')
+        if theta.dtype != np.float64:
+            return declined('dtype')
+        if not (dev.lib_provides('tpa_gemm_chain_ex') and hasattr(dev.lib(), 'tpa_gemm_kernel_id')):
+            return declined('library')
+        key = (id(p1), id(a01), id(p2))
+        hit = _skip_table_cache.get(key)
+        if hit is not None and hit[0] is p1 and hit[1] is a01 and hit[2] is p2:
+            _skip_table_cache.move_to_end(key)
+            et = hit[3]
+        else:
+            et = self._skip_tables(fp)
+            _skip_table_cache[key] = (p1, a01, p2, et)          # (the plans stay alive with their ids)
+            if len(_skip_table_cache) > 1024:
+                _skip_table_cache.popitem(last=False)
+        if isinstance(et, str):
+            return declined(et)
+        kb.stats['n_skip_taken'] += 1
+        bufs = [self._LPf._arena, self._RPf._arena, dev.scratch('lanczos_t1', p1.res_total, p1.dtype),
+                dev.scratch('lanczos_t3', a01.total, a01.dtype)]
+        if et['a_tiles'] is None:
+            ops = _gemm_ops(p1, 0, -1, 2, bufs, 'lanczos_sk1')
+        elif p1.sk is None:
+            ops = [[0, p1.cfg, p1.tasks_dev.data_ptr(), p1.links_dev.data_ptr(), et['a_tiles'].data_ptr(), len(et['a_tiles']), 0, -1, 2, 0, 0, 0]]
+        else:
+            sk = p1.sk
+            bufs.append(dev.scratch('lanczos_sk1', sk.total, p1.dtype))
+            ops = [[0, p1.cfg, sk.tasks_dev.data_ptr(), sk.links_dev.data_ptr(), et['a_tiles'].data_ptr(), len(et['a_tiles']), 0, -1,
+                    len(bufs) - 1, 0, 0, 0],
+                   [1, 1, et['a_jobs'].data_ptr(), sk.terms_dev.data_ptr(), 0, len(et['a_jobs']), len(bufs) - 1, 0, 2, sk.max_elems, 0, 0]]
+        if et['b_jobs'] is not None:
+            ops.append([1, 0, et['b_jobs'].data_ptr(), a01.terms_dev.data_ptr(), 0, len(et['b_jobs']), 2, 0, 3, a01.max_elems, 0, 0])
+        sk = p2.sk
+        if sk is None:
+            ops.append([7, p2.cfg, p2.tasks_dev.data_ptr(), et['c_links'].data_ptr(), p2.tiles_dev.data_ptr(), p2.n_tiles, 3, 1, -2, 2,
+                        et['alphas'].data_ptr(), 0])
+        else:
+            bufs.append(dev.scratch('lanczos_sk2', sk.total, p2.dtype))
+            part = len(bufs) - 1
+            ops.append([7, p2.cfg, sk.tasks_dev.data_ptr(), et['c_links'].data_ptr(), sk.tiles_dev.data_ptr(), sk.n_tiles, 3, 1, part, 2,
+                        et['alphas'].data_ptr(), 0])
+            ops.append([1, 1, sk.jobs_dev.data_ptr(), sk.terms_dev.data_ptr(), 0, sk.n_jobs, part, 0, -2, sk.max_elems, 0, 0])
+        self.flops_per_matvec = et['plan_a'].flops + p2.flops
+        self.bytes_per_matvec = et['plan_a'].bytes_min + p2.bytes_min + et['b_bytes']
+        self.gemm_shapes = (et['plan_a'].gemm_shapes, p2.gemm_shapes)
+        return (np.array(ops, dtype=np.int64), bufs, (et['plan_a'], p2))
+
+    @staticmethod
+    def _skip_tables(fp):
+        """The tables of :meth:`_skip_program` (numpy only, no device read-back): a dict, or the reason (a string) why there is nothing
+        to skip or to build."""
+        p1, a01, p2 = fp['p1'], fp['a01'], fp['p2']
+        jobs3, terms3 = a01.jobs_host, a01.terms_host
+        t1_off = np.asarray(p1.res_offsets, dtype=np.int64)
+        term_t1 = np.searchsorted(t1_off, terms3[:, 0])
+        if not np.array_equal(t1_off[np.minimum(term_t1, len(t1_off) - 1)], terms3[:, 0]):
+            return 'term_inside_block'
+        # ---- step 2: a link over a single-term block of T3 reads the block of T1 (a split-K part: the same cut of it)
+        order = np.argsort(jobs3[:, 0])
+        j_off, j_size = jobs3[order, 0], jobs3[order, 1] * jobs3[order, 2]
+        single, first_term = jobs3[order, 5] == 1, jobs3[order, 4]
+        links = (p2.links_host if p2.sk is None else p2.sk.links_host).copy()
+        lj = np.clip(np.searchsorted(j_off, links[:, 0], side='right') - 1, 0, len(j_off) - 1)
+        inside = (links[:, 0] >= j_off[lj]) & (links[:, 0] < j_off[lj] + j_size[lj])
+        if not np.all(inside | (links[:, 2] <= 0)):
+            return 'link_outside_blocks'
+        swap = inside & single[lj] & (links[:, 2] > 0)
+        term = first_term[lj[swap]]
+        if np.any(terms3[term, 1] != j_size[lj[swap]]):
+            return 'term_shape'
+        alpha = terms3[:, 2:4].copy().view(np.float64)[:, 0]
+        ualpha, ai = np.unique(alpha[term], return_inverse=True)
+        if len(ualpha) + 1 > 0xffff:
+            return 'too_many_coefficients'
+        alphas = np.zeros(2 * (len(ualpha) + 1), dtype=np.float64)
+        alphas[0], alphas[2::2] = 1., ualpha
+        links[swap, 0] = terms3[term, 0] + (links[swap, 0] - j_off[lj[swap]])
+        links[swap, 7] = (links[swap, 7] & 3) | 4 | ((ai.reshape(-1) + 1) << 16)
+        multi = np.sort(order[~single])
+        et = dict(a_tiles=None, a_jobs=None, b_jobs=None)
+        b_elems = 0
+        if len(multi):
+            in_multi = np.zeros(len(terms3), dtype=bool)
+            starts, counts = jobs3[multi, 4], jobs3[multi, 5]
+            in_multi[np.repeat(starts, counts) + np.arange(int(np.sum(counts))) - np.repeat(np.cumsum(counts) - counts, counts)] = True
+            b_elems = int(np.sum(terms3[in_multi, 1]) + np.sum(jobs3[multi, 1] * jobs3[multi, 2]))
+        # ---- step 1: the tiles of the blocks of T1 that are read
+        need = np.zeros(len(t1_off), dtype=bool)
+        need[term_t1] = True
+        plan_a = p1
+        if not np.all(need):
+            sk, t1 = p1.sk, p1.tasks_host
+            src = p1.tiles_host if sk is None else sk.tiles_host
+            tile_task = src[:, 0] if sk is None else np.repeat(np.arange(len(t1_off)), sk.parts)[src[:, 0]]
+            kept = np.ascontiguousarray(src[need[tile_task]])
+            kernel = dev.lib().tpa_gemm_kernel_id
+            if kernel(dev.code(p1.dtype), p1.cfg, len(kept)) == kernel(dev.code(p1.dtype), p1.cfg, len(src)):
+                cnt = t1[need, 5]
+                lk = np.repeat(t1[need, 4], cnt) + np.arange(int(np.sum(cnt))) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+                mt, nt_, kk = np.repeat(t1[need, 1], cnt), np.repeat(t1[need, 2], cnt), p1.links_host[lk, 2]
+                _, ua = np.unique(p1.links_host[lk, 0], return_index=True)
+                _, ub = np.unique(p1.links_host[lk, 1], return_index=True)
+                from types import SimpleNamespace
+                plan_a = SimpleNamespace(flops=int(2 * np.sum(mt * kk * nt_)), gemm_shapes=np.stack([mt, kk, nt_], axis=1),
+                                         bytes_min=int(8 * (np.sum(mt[ua] * kk[ua]) + np.sum(kk[ub] * nt_[ub]) + np.sum(t1[need, 1] * t1[need, 2]))))
+                if sk is None:
+                    (et['a_tiles'],) = dev.to_device_packed(kept)
+                else:
+                    et['a_tiles'], et['a_jobs'] = dev.to_device_packed(kept, np.ascontiguousarray(sk.jobs_host[need]))
+        if et['a_tiles'] is None and not np.any(swap):
+            return 'nothing_to_skip'
+        if len(multi):
+            et['c_links'], et['alphas'], et['b_jobs'] = dev.to_device_packed(links, alphas, np.ascontiguousarray(jobs3[multi]))
+        else:
+            et['c_links'], et['alphas'] = dev.to_device_packed(links, alphas)
+        et['plan_a'], et['b_bytes'], et['n_swapped'] = plan_a, 8 * b_elems, int(np.sum(swap))
+        return et
 
     def update_LP(self, env, i, U=None):
         """LP(i0+1) = U^dagger LHeff U   (reference :1421)."""

@@ -23,6 +23,39 @@ struct Task {  // int64[8]
     int64_t c_off, m, n, ldc, link_begin, link_count, accumulate, pad;
 };
 
+// EXTENDED LINKS (tpa_gemm_chain_ex; the EX instantiations of both kernels -- the plain ones compile none of this):
+//   flags bit 2     : the A operand of the link is read from A2base instead of Abase
+//   flags bit 3     : B is the unit matrix -- stored with k = 0, so the k loop steps over the link; the epilogue adds
+//                     alpha * A(row, col) from global memory
+//   flags bits 16-31: index i into `alphas` (pairs of doubles, real data uses the first of a pair); 0 = no scale.  The elements of A are
+//                     multiplied by alphas[2 i] on their way into LDS: fma(alpha, a, 0), the single-term product of lincomb_kernel
+constexpr int64_t LINK_A2 = 4, LINK_UNIT = 8;
+__device__ __forceinline__ double link_alpha(const Link &L, const double *__restrict__ alphas) {
+    const int ia = (int)((L.flags >> 16) & 0xffff);
+    return ia ? alphas[2 * ia] : 1.0;
+}
+// the unit-factor links of a chain, added to the accumulators in their C / D layout (row = row_base + 4 r, col) before the epilogue
+template <int TM, int TN>
+__device__ __forceinline__ void add_unit_links(d4 (&acc)[TM][TN], const Link *__restrict__ lk, const int nl, const double *__restrict__ Abase,
+                                               const double *__restrict__ A2base, const double *__restrict__ alphas, const int row_base,
+                                               const int col_base, const int m, const int n) {
+    for (int l = 0; l < nl; ++l) {
+        const Link L = lk[l];
+        if (!(L.flags & LINK_UNIT)) continue;
+        const double al = link_alpha(L, alphas);
+        const double *src = ((L.flags & LINK_A2) ? A2base : Abase) + L.a_off;
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = row_base + i * 16 + 4 * r, col = col_base + j * 16;
+                    if (row < m && col < n) acc[i][j][r] = fma(al, src[(int64_t)row * L.a_rs + (int64_t)col * L.a_ks], acc[i][j][r]);
+                }
+    }
+}
+
 // IDENTITY-ROW SKIP (round 6; used by the block SVD's product [W | G] <- Qtot [W | G], tpa_svd.hip: svd_run): a tile with tile.w > 0 of a
 // task with pad != 0 looks at the word ((const int *)pad)[tile.w - 1]; 0 means "the rows of A that this tile of C needs are unit vectors
 // e_row" (those rows of Qtot did not rotate in the sweep), so C[row, :] = B[row, :] and the tile is a COPY of the first link's B operand
@@ -73,10 +106,12 @@ struct Stage {
     int i0, istep, lim;   // row (A) / column (B) index of element r = i0 + r * istep, valid while < lim
 };
 
-template <bool CPLX, int BM, int BN, int TM, int TN, int BK_>
+template <bool CPLX, int BM, int BN, int TM, int TN, int BK_, bool EX = false>
 __global__ __launch_bounds__((Cfg<CPLX, BM, BN, TM, TN, BK_>::NT)) void gemm_chain_kernel(
     const Task *__restrict__ tasks, const Link *__restrict__ links, const int4 *__restrict__ tiles,
-    const double *__restrict__ Abase, const double *__restrict__ Bbase, double *__restrict__ Cbase) {
+    const double *__restrict__ Abase, const double *__restrict__ Bbase, double *__restrict__ Cbase,
+    const double *__restrict__ A2base, const double *__restrict__ alphas) {
+    static_assert(!(EX && CPLX), "extended links: real data only");
     using C = Cfg<CPLX, BM, BN, TM, TN, BK_>;
     constexpr int NT = C::NT, EA = C::EA, EB = C::EB, PL = C::PLANES, BK = C::BK;
     constexpr int ES = CPLX ? 2 : 1;  // doubles per element
@@ -110,6 +145,7 @@ __global__ __launch_bounds__((Cfg<CPLX, BM, BN, TM, TN, BK_>::NT)) void gemm_cha
         Stage a, b;
         int K, sa_i, sa_k, sb_j, sb_k;
         double sgn_a, sgn_b;
+        double al;                   // (EX) scale of the A elements
         int64_t oa[EA], ob[EB];      // element offsets (doubles) relative to a.p / b.p, fixed per link
     };
     auto open_link = [&](int li, LinkView &v) {
@@ -119,6 +155,8 @@ __global__ __launch_bounds__((Cfg<CPLX, BM, BN, TM, TN, BK_>::NT)) void gemm_cha
         const bool b_kfast = (L.b_ks == 1) && (L.b_ns != 1);
         v.sgn_a = (CPLX && (L.flags & 1)) ? -1.0 : 1.0;
         v.sgn_b = (CPLX && (L.flags & 2)) ? -1.0 : 1.0;
+        const double *Asrc = (EX && (L.flags & LINK_A2)) ? A2base : Abase;
+        if (EX) v.al = link_alpha(L, alphas);
         v.sa_i = a_kfast ? (BK + 1) : 1;
         v.sa_k = a_kfast ? 1 : (BM + C::PADA);
         v.sb_j = b_kfast ? (BK + 1) : 1;
@@ -126,7 +164,7 @@ __global__ __launch_bounds__((Cfg<CPLX, BM, BN, TM, TN, BK_>::NT)) void gemm_cha
         {   // A: element e = tid + r NT;  k-fast: (i, kk) = (e / BK, e % BK);  else (e % BM, e / BM)
             const int i = a_kfast ? (tid / BK) : (tid % BM), kk = a_kfast ? (tid % BK) : (tid / BM);
             const int di = a_kfast ? (NT / BK) : 0, dk = a_kfast ? 0 : (NT / BM);
-            v.a.p = Abase + ES * (L.a_off + (int64_t)(row0 + i) * L.a_rs + (int64_t)kk * L.a_ks);
+            v.a.p = Asrc + ES * (L.a_off + (int64_t)(row0 + i) * L.a_rs + (int64_t)kk * L.a_ks);
             v.a.gstep = ES * ((int64_t)di * L.a_rs + (int64_t)dk * L.a_ks);
             v.a.kstep = ES * (int64_t)BK * L.a_ks;
             v.a.lbase = i * v.sa_i + kk * v.sa_k;
@@ -192,7 +230,7 @@ __global__ __launch_bounds__((Cfg<CPLX, BM, BN, TM, TN, BK_>::NT)) void gemm_cha
 #pragma unroll
         for (int r = 0; r < EA; ++r)
 #pragma unroll
-            for (int p = 0; p < PL; ++p) Ad[p * C::A_LDS + v.a.lbase + r * v.a.lstep] = ra[p][r];
+            for (int p = 0; p < PL; ++p) Ad[p * C::A_LDS + v.a.lbase + r * v.a.lstep] = EX ? fma(v.al, ra[p][r], 0.0) : ra[p][r];
 #pragma unroll
         for (int r = 0; r < EB; ++r)
 #pragma unroll
@@ -258,6 +296,8 @@ __global__ __launch_bounds__((Cfg<CPLX, BM, BN, TM, TN, BK_>::NT)) void gemm_cha
         }
     }
 
+    if constexpr (EX) add_unit_links<TM, TN>(acc[0], lk, nl, Abase, A2base, alphas, row0 + wr * TM * 16 + l4, col0 + wc * TN * 16 + l15, m, n);
+
     // ---- epilogue: C/D layout of v_mfma_f64_16x16x4_f64: col = lane&15, row = (lane>>4) + 4*reg
     double *Cp = Cbase + ES * tk.c_off;
     const bool accum = tk.accumulate != 0;
@@ -312,11 +352,12 @@ struct Cfg2 {
     static_assert(NT % BK == 0 && NT % BM == 0 && NT % BN == 0, "staging offsets must be affine in the element index");
 };
 
-template <int BM, int BN, int TM, int TN>
+template <int BM, int BN, int TM, int TN, bool EX = false>
 __global__ __launch_bounds__((Cfg2<BM, BN, TM, TN>::NT)) __attribute__((amdgpu_waves_per_eu(TM * TN >= 16 ? 2 : (TM * TN >= 8 ? 3 : 4))))
 void gemm_chain2_kernel(
     const Task *__restrict__ tasks, const Link *__restrict__ links, const int4 *__restrict__ tiles,
-    const double *__restrict__ Abase, const double *__restrict__ Bbase, double *__restrict__ Cbase) {
+    const double *__restrict__ Abase, const double *__restrict__ Bbase, double *__restrict__ Cbase,
+    const double *__restrict__ A2base, const double *__restrict__ alphas) {
     using C = Cfg2<BM, BN, TM, TN>;
     constexpr int NT = C::NT, EA = C::EA, EB = C::EB, BK = C::BK, LD = C::LD, IMG = C::IMG;
     extern __shared__ double lds2[];
@@ -349,16 +390,18 @@ void gemm_chain2_kernel(
         int kka, dka, kkb, dkb;      // k index inside the tile of element r: kk + r * dk (tail predicate)
         int la, dla, lb, dlb;        // LDS offset of element r: l + r * dl (doubles, inside an operand plane)
         int K;
+        double al;                   // (EX) scale of the A elements
     };
     auto open_link = [&](int li, View &v) {
         const Link L = lk[li];
         v.K = (int)L.k;
+        if (EX) v.al = link_alpha(L, alphas);
         const bool a_kfast = (L.a_ks == 1);
         const bool b_kfast = (L.b_ks == 1) && (L.b_ns != 1);
         {   // element e = tid + r NT;  k-fast: (i, kk) = (e / BK, e % BK);  else (e % BM, e / BM)
             const int i = a_kfast ? (tid / BK) : (tid % BM), kk = a_kfast ? (tid % BK) : (tid / BM);
             const int di = a_kfast ? (NT / BK) : 0, dk = a_kfast ? 0 : (NT / BM);
-            v.pa = Abase + L.a_off;
+            v.pa = ((EX && (L.flags & LINK_A2)) ? A2base : Abase) + L.a_off;
             v.ka = (int64_t)BK * L.a_ks;
             v.kka = kk;
             v.dka = dk;
@@ -401,7 +444,7 @@ void gemm_chain2_kernel(
     };
     auto store_tile = [&](const View &v, double *img) {
 #pragma unroll
-        for (int r = 0; r < EA; ++r) img[v.la + r * v.dla] = ra[r];
+        for (int r = 0; r < EA; ++r) img[v.la + r * v.dla] = EX ? fma(v.al, ra[r], 0.0) : ra[r];
 #pragma unroll
         for (int r = 0; r < EB; ++r) img[C::A_LDS + v.lb + r * v.dlb] = rb[r];
     };
@@ -473,6 +516,8 @@ void gemm_chain2_kernel(
         }
     }
 
+    if constexpr (EX) add_unit_links<TM, TN>(acc, lk, nl, Abase, A2base, alphas, row0 + wr * TM * 16 + l4, col0 + wc * TN * 16 + l15, m, n);
+
     // ---- epilogue: C/D layout of v_mfma_f64_16x16x4_f64: col = lane&15, row = (lane>>4) + 4*reg
     double *Cp = Cbase + tk.c_off;
     const bool accum = tk.accumulate != 0;
@@ -511,28 +556,38 @@ extern "C" int tpa_gemm_tile_shape(int dtype, int cfg, int *bm, int *bn) {
     return 0;
 }
 
-template <bool CPLX, int BM, int BN, int TM, int TN, int BK_>
-static void launch(const int64_t *tasks_dev, const int64_t *links_dev, const int32_t *tiles_dev, int n_tiles,
-                   const void *Abase, const void *Bbase, void *Cbase, hipStream_t st) {
-    using C = Cfg<CPLX, BM, BN, TM, TN, BK_>;
-    gemm_chain_kernel<CPLX, BM, BN, TM, TN, BK_><<<n_tiles, C::NT, 0, st>>>(
-        (const Task *)tasks_dev, (const Link *)links_dev, (const int4 *)tiles_dev, (const double *)Abase,
-        (const double *)Bbase, (double *)Cbase);
+// Which kernel a launch of n_tiles tiles runs on (the one place that knows the switch): 0 = gemm_chain_kernel (eight wavefronts per
+// tile for real data), 1 = gemm_chain2_kernel.  See the measurements in tpa_gemm_chain.
+extern "C" int tpa_gemm_kernel_id(int dtype, int cfg, int n_tiles) {
+    if (dtype != TPA_F64) return 0;
+    if (cfg == 0) return 1;
+    return (n_tiles <= 1024 && !(g_variant & 1)) ? 0 : 1;
 }
 
-template <int BM, int BN, int TM, int TN>
+template <bool CPLX, int BM, int BN, int TM, int TN, int BK_, bool EX = false>
+static void launch(const int64_t *tasks_dev, const int64_t *links_dev, const int32_t *tiles_dev, int n_tiles,
+                   const void *Abase, const void *Bbase, void *Cbase, hipStream_t st, const void *A2base = nullptr,
+                   const double *alphas = nullptr) {
+    using C = Cfg<CPLX, BM, BN, TM, TN, BK_>;
+    gemm_chain_kernel<CPLX, BM, BN, TM, TN, BK_, EX><<<n_tiles, C::NT, 0, st>>>(
+        (const Task *)tasks_dev, (const Link *)links_dev, (const int4 *)tiles_dev, (const double *)Abase,
+        (const double *)Bbase, (double *)Cbase, (const double *)A2base, alphas);
+}
+
+template <int BM, int BN, int TM, int TN, bool EX = false>
 static int launch2(const int64_t *tasks_dev, const int64_t *links_dev, const int32_t *tiles_dev, int n_tiles,
-                   const void *Abase, const void *Bbase, void *Cbase, hipStream_t st) {
+                   const void *Abase, const void *Bbase, void *Cbase, hipStream_t st, const void *A2base = nullptr,
+                   const double *alphas = nullptr) {
     using C = Cfg2<BM, BN, TM, TN>;
     static bool attr_set = false;      // more than 64 KB of LDS per workgroup must be asked for (once per instantiation)
     if (!attr_set) {
-        TPA_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_chain2_kernel<BM, BN, TM, TN>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        TPA_HIP_CHECK(hipFuncSetAttribute((const void *)gemm_chain2_kernel<BM, BN, TM, TN, EX>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                           C::LDS_BYTES));
         attr_set = true;
     }
-    gemm_chain2_kernel<BM, BN, TM, TN><<<n_tiles, C::NT, C::LDS_BYTES, st>>>(
+    gemm_chain2_kernel<BM, BN, TM, TN, EX><<<n_tiles, C::NT, C::LDS_BYTES, st>>>(
         (const Task *)tasks_dev, (const Link *)links_dev, (const int4 *)tiles_dev, (const double *)Abase,
-        (const double *)Bbase, (double *)Cbase);
+        (const double *)Bbase, (double *)Cbase, (const double *)A2base, alphas);
     return 0;
 }
 
@@ -554,7 +609,7 @@ extern "C" int tpa_gemm_chain(int dtype, int cfg, const int64_t *tasks_dev, cons
         // on 2 x 2 or 1 x 2 MFMA tiles per wavefront is 5 % slower there (chi = 512: 12.8 / 13.5 against 13.5 TFLOP/s).  g_variant bit 0 = new loop everywhere.
         if (cfg == 0)
             rc = launch2<128, 64, 4, 2>(tasks_dev, links_dev, tiles_dev, n_tiles, Abase, Bbase, Cbase, st);
-        else if (n_tiles <= 1024 && !(g_variant & 1))
+        else if (tpa_gemm_kernel_id(dtype, cfg, n_tiles) == 0)
             launch<false, 64, 64, 1, 2, 16>(tasks_dev, links_dev, tiles_dev, n_tiles, Abase, Bbase, Cbase, st);
         else
             rc = launch2<64, 64, 2, 2>(tasks_dev, links_dev, tiles_dev, n_tiles, Abase, Bbase, Cbase, st);
@@ -564,6 +619,28 @@ extern "C" int tpa_gemm_chain(int dtype, int cfg, const int64_t *tasks_dev, cons
         else
             launch<true, 128, 64, 4, 2, 16>(tasks_dev, links_dev, tiles_dev, n_tiles, Abase, Bbase, Cbase, st);
     }
+    if (rc) return rc;
+    TPA_LAUNCH_CHECK();
+    return 0;
+}
+
+// The grouped GEMM with extended links (second source, scale, unit factor: see LINK_A2 above and include/tenpy_amd.h).  Real data; the
+// same dispatch over the two kernels as tpa_gemm_chain.
+extern "C" int tpa_gemm_chain_ex(int dtype, int cfg, const int64_t *tasks_dev, const int64_t *links_dev, const int32_t *tiles_dev,
+                                 int n_tiles, const void *Abase, const void *A2base, const void *Bbase, void *Cbase,
+                                 const double *alphas_dev, void *stream) {
+    TPA_ARG_CHECK(dtype == TPA_F64);
+    TPA_ARG_CHECK(cfg == 0 || cfg == 1);
+    TPA_ARG_CHECK(A2base != nullptr && alphas_dev != nullptr);
+    if (n_tiles <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = 0;
+    if (cfg == 0)
+        rc = launch2<128, 64, 4, 2, true>(tasks_dev, links_dev, tiles_dev, n_tiles, Abase, Bbase, Cbase, st, A2base, alphas_dev);
+    else if (tpa_gemm_kernel_id(dtype, cfg, n_tiles) == 0)
+        launch<false, 64, 64, 1, 2, 16, true>(tasks_dev, links_dev, tiles_dev, n_tiles, Abase, Bbase, Cbase, st, A2base, alphas_dev);
+    else
+        rc = launch2<64, 64, 2, 2, true>(tasks_dev, links_dev, tiles_dev, n_tiles, Abase, Bbase, Cbase, st, A2base, alphas_dev);
     if (rc) return rc;
     TPA_LAUNCH_CHECK();
     return 0;

@@ -736,8 +736,10 @@ extern "C" int tpa_lanczos_run_ex(int dtype, int64_t n, const int64_t *ops, int 
         for (int o = 0; o < n_ops; ++o) {
             const int64_t *op = ops + 12 * o;
             void *a = lz_slot(op[6], bufs, n_bufs, vin, w), *b = lz_slot(op[7], bufs, n_bufs, vin, w), *c = lz_slot(op[8], bufs, n_bufs, vin, w);
-            if (op[0] == 0) {
+            if (op[0] == 0 || op[0] == 7) {     // 7: kind 0 through tpa_gemm_chain_ex (op[9] = slot of A2, op[10] = alphas)
                 TPA_ARG_CHECK(a != nullptr && b != nullptr && c != nullptr);
+                const void *a2 = op[0] == 7 ? lz_slot(op[9], bufs, n_bufs, vin, w) : nullptr;
+                TPA_ARG_CHECK(op[0] == 0 || (a2 != nullptr && op[10] != 0));
                 if (time_gemms) {
                     while (H.tev.size() < n_tev + 2) {
                         hipEvent_t e;
@@ -746,8 +748,10 @@ extern "C" int tpa_lanczos_run_ex(int dtype, int64_t n, const int64_t *ops, int 
                     }
                     TPA_HIP_CHECK(hipEventRecord(H.tev[n_tev], st));
                 }
-                if (int rc = tpa_gemm_chain(dtype, (int)op[1], (const int64_t *)op[2], (const int64_t *)op[3], (const int32_t *)op[4], (int)op[5],
-                                            a, b, c, stream))
+                if (int rc = op[0] == 0 ? tpa_gemm_chain(dtype, (int)op[1], (const int64_t *)op[2], (const int64_t *)op[3],
+                                                         (const int32_t *)op[4], (int)op[5], a, b, c, stream)
+                                        : tpa_gemm_chain_ex(dtype, (int)op[1], (const int64_t *)op[2], (const int64_t *)op[3],
+                                                            (const int32_t *)op[4], (int)op[5], a, a2, b, c, (const double *)op[10], stream))
                     return rc;
                 if (time_gemms) {
                     TPA_HIP_CHECK(hipEventRecord(H.tev[n_tev + 1], st));

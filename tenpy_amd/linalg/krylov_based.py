@@ -32,7 +32,10 @@ __all__ = ['LanczosGroundState', 'LanczosEvolution', 'Arnoldi', 'lanczos', 'gram
 
 
 stats = {'runs': 0, 'n_matvec': 0, 'n_ill_conditioned': 0, 'n_degenerate': 0, 'n_native_sharded': 0, 'n_native_evolve': 0,
-         'n_native_ortho': 0, 'n_ortho_declined': 0, 'n_native_reortho': 0}
+         'n_native_ortho': 0, 'n_ortho_declined': 0, 'n_native_reortho': 0,
+         # launch programs of TwoSiteH without the work nobody reads (algorithms/mps_common.py: `_skip_program`): built, declined
+         'n_skip_taken': 0, 'n_skip_declined': 0}
+skip_declined = {}                  # reason -> count of the declined programs
 
 
 class LanczosGroundState:

@@ -1653,6 +1653,7 @@ def clear_device_caches():
         _mc.MpoApplyPlan._cache.clear()
         _mc.MpoBlockApplyPlan._cache.clear()
         _mc.MpoEntryApplyPlan._cache.clear()
+        _mc._skip_table_cache.clear()
     except ImportError:      # (the linalg package is importable on its own)
         pass
 
@@ -2263,7 +2264,7 @@ def _build_plan(a, b, ca, cb, fa, fb):
     tiles = np.zeros((len(t_task), 4), dtype=np.int32)
     tiles[:, 0], tiles[:, 1], tiles[:, 2] = t_task[order], t_row[order], t_col[order]
     plan.n_tiles = len(tiles)
-    plan.tasks_host, plan.links_host = tasks, links
+    plan.tasks_host, plan.links_host, plan.tiles_host = tasks, links, tiles
     plan.tasks_dev, plan.links_dev, plan.tiles_dev = dev.to_device_packed(tasks, links, tiles)
     cmul = 8 if plan.dtype.kind == 'c' else 2
     plan.flops = int(cmul * np.sum(M[ga] * K[ga] * N[gb]))
@@ -2290,7 +2291,7 @@ GEMM_K_TILE = 16
 
 class _SplitK:
     __slots__ = ('tasks_dev', 'links_dev', 'tiles_dev', 'n_tiles', 'total', 'jobs_dev', 'terms_dev', 'n_jobs', 'max_elems',
-                 'tasks_host', 'links_host', 'jobs_host', 'terms_host', 'parts')
+                 'tasks_host', 'links_host', 'jobs_host', 'terms_host', 'parts', 'tiles_host')
 
 
 def _split_k(plan, tasks, links, tm, tn, knob=None):
@@ -2361,7 +2362,7 @@ def _split_k(plan, tasks, links, tm, tn, knob=None):
                             np.repeat(tn_new, ntile))
     tiles = np.zeros((len(t_task), 4), dtype=np.int32)
     tiles[:, 0], tiles[:, 1], tiles[:, 2] = t_task[order], t_row[order], t_col[order]
-    sk.tasks_host, sk.links_host, sk.jobs_host, sk.terms_host = new_tasks, new_links, jobs, terms
+    sk.tasks_host, sk.links_host, sk.jobs_host, sk.terms_host, sk.tiles_host = new_tasks, new_links, jobs, terms, tiles
     sk.tasks_dev, sk.links_dev, sk.tiles_dev, sk.jobs_dev, sk.terms_dev = dev.to_device_packed(sk.tasks_host, sk.links_host, tiles, sk.jobs_host,
                                                                                             sk.terms_host)
     sk.n_tiles, sk.total, sk.n_jobs = len(tiles), off, len(jobs)
