@@ -305,6 +305,30 @@ int tpa_mpo_apply_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const in
  * 16-byte aligned and, for F64, post, dst_off, dst_ld and every src_off and src_ld of the job are even; 8-byte ones otherwise. */
 int tpa_mpo_entry_apply_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const int64_t *rows_dev, const int64_t *terms_dev,
                               int64_t max_job_cols, const void *src_base, void *dst_base, void *stream);
+/* tpa_mpo_entry_apply_batch with a destination offset per row and a second source: the fused matrix of the subspace expansion of
+ * single-site DMRG in ONE pass.  It replaces the build of LHeff / RHeff, iscale_axis with the mixing weights, the tensordot over the
+ * fused leg and combine_legs of SubspaceExpansion (reference mps_common.py:2140-2168, right move, and :2170-2199, left move): the
+ * source is T1 = LP . theta (theta . RP), a job is one cell (row slice x column slice) of a charge block of the fused matrix
+ * [(vL.p0), (wR.vR)] ([(vL.wL), (p0.vR)]), and the rows (p0', wR') of a cell lie one leading dimension apart for p0' and in other
+ * column slices for wR' -- no (pre, n_rows, post) slab holds them.  The mixing weight is multiplied into alpha on the host.
+ * jobs : int64[n_jobs][8] = {dst_off, pre, n_rows, post, row_begin, dst_ld, 0, 0}     dst_ld is used as it is (no default)
+ * rows : int64[..][4]     = {term_begin, term_count, dst_row_off, src_sel}            row o of a job: rows[row_begin + o], o < n_rows
+ * terms: int64[..][4]     = {src_off, src_ld, alpha_re, alpha_im}                     the terms of tpa_lincomb_batch (bit patterns)
+ *   dst[dst_off + i*dst_ld + dst_row_off_o + j] = sum_t alpha_t * SRC_o[src_off_t + i*src_ld_t + j]     for i < pre, o < n_rows, j < post
+ *   SRC_o = src_base if src_sel_o == 0 else src2_base    (the stacked form, IdL / IdR = None: the rows of theta itself read src2)
+ * Offsets and strides in elements of dtype.  max_job_cols = max pre * post over the jobs sizes the grid, capped at 512 workgroups per
+ * job (larger jobs loop).  One job per blockIdx.y like the other batched entry points of this section: dtype is checked first, then
+ * n_jobs <= 0 returns 0 without a launch and n_jobs > 65535 returns TPA_E_BADARG; all argument errors before anything is launched; jobs
+ * with a zero extent do nothing.  Exactly the listed elements are written, each once -- the caller guarantees that the rows of a launch
+ * do not overlap; a row with term_count = 0 writes zeros --, nothing else is written; src, src2 and dst must not overlap; src2_base is
+ * read only by rows that select it (it may be NULL when none does).  Summation order: the terms of a row in table order, one chain of
+ * fused multiply-adds per component (real: term_count, complex: twice that) -- two identical calls give identical bits.  A thread owns
+ * one column item (i, j) of its job and walks the job's rows with one accumulator; row and term tables go through uniform loads.
+ * Traffic: itemsize (sum_terms pre post + sum_rows pre post) bytes.  16-byte loads and stores where src_base, src2_base and dst_base
+ * are 16-byte aligned and, for F64, post, dst_off, dst_ld and every dst_row_off, src_off and src_ld of the job are even (decided per
+ * job); 8-byte ones otherwise. */
+int tpa_mpo_expand_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const int64_t *rows_dev, const int64_t *terms_dev,
+                         int64_t max_job_cols, const void *src_base, const void *src2_base, void *dst_base, void *stream);
 /* x_b[i, j, l] *= s[s_off_b + j]  for each block b viewed as (pre, len, post).  Replaces
  * iscale_axis, np_conserved.py:2132-2140.  jobs: int64[n][6] = {x_off, pre, len, post, s_off, 0};
  * the scale vector s is real (F64) or of `dtype` when s_is_complex. */

@@ -56,6 +56,7 @@ _SIGS = {
     "tpa_lincomb_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp, _vp]),
     "tpa_mpo_apply_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp]),
     "tpa_mpo_entry_apply_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp]),
+    "tpa_mpo_expand_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     "tpa_svd_dyn_stats": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "tpa_tri_lower_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int64, _vp, _vp]),
     "tpa_scale_axis_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp]),

@@ -1,4 +1,4 @@
-"""Minimal two-site DMRG driver for boxes WITHOUT TeNPy (the GPU test box: ``bench.py``, ``smoke()``, the ``-m gpu`` tests).
+"""Minimal two-site (and single-site) DMRG driver for boxes WITHOUT TeNPy (the GPU test box: ``bench.py``, ``smoke()``, the ``-m gpu`` tests).
 
 Where TeNPy is installed, use TeNPy's own engines on the device mirror instead -- ``tenpy_amd.install.install()`` and then
 ``tenpy.algorithms.dmrg.TwoSiteDMRGEngine`` etc. run unchanged (mixers, single-site DMRG, infinite systems, excited states:
@@ -11,6 +11,9 @@ Options (names as in the reference): ``trunc_params``, ``lanczos_params``, ``chi
 ``'DensityMatrixMixer'`` / ``None``, default ``None``), ``mixer_params`` (``amplitude``, ``decay``, ``disable_after``),
 ``chi_list_reactivates_mixer`` (default on: a step of ``chi_list`` switches the mixer on again, reference mps_common.py ``sweep``);
 ``shard_matvec`` (multi-GPU, ``algorithms/sharded.py``; with ``krylov_row_panels`` the Krylov vectors are row panels), ``profile`` (per-phase timers; synchronises the device).
+
+``SingleSiteDMRGEngine`` (end of the file) is the single-site engine on the same footing: the reference's schedule and statements for
+one optimised site, the device ``OneSiteH``, and the subspace expansion of ``algorithms/mixer.py`` as its mixer (on by default).
 
 ``orthogonal_to=[MPS, ...]`` (keyword, off by default; not with ``shard_matvec``): the search stays orthogonal to the given states
 (reference ``mps_common.py:521-540``) -- the minimum the GPU tests of the projected Lanczos loop need, not an excited-state engine.
@@ -26,9 +29,9 @@ from ..linalg import np_conserved as npc
 from ..linalg.krylov_based import LanczosGroundState
 from ..linalg.truncation import svd_theta
 from ..networks.mpo import MPOEnvironment
-from .mps_common import TwoSiteH
+from .mps_common import OneSiteH, TwoSiteH
 
-__all__ = ['TwoSiteDMRGEngine']
+__all__ = ['TwoSiteDMRGEngine', 'SingleSiteDMRGEngine']
 
 
 _GC_PAUSE = os.environ.get('TPA_SWEEP_GC_PAUSE', '1') != '0'
@@ -43,6 +46,9 @@ def _plus_hc(eff_H):
 
 
 class TwoSiteDMRGEngine:
+    DefaultMixer = 'DensityMatrixMixer'
+    use_mixer_by_default = False
+
     def _warm_token(self):
         """Key of this engine's warm-start bases (``linalg/_svd_warm.owner_token``: unique for the life of the engine, released with it)."""
         from ..linalg import _svd_warm
@@ -76,9 +82,10 @@ class TwoSiteDMRGEngine:
             if dist.is_initialized() and (dist.get_world_size() > 1 or os.environ.get('TPA_SHARD_FORCE')):
                 self._svd_group = (None, dist.get_rank(), dist.get_world_size())
         self.mixer = None
-        self._mixer_on = options.get('mixer') not in (None, False)
-        if options.get('mixer') not in (None, False, True, 'DensityMatrixMixer'):
-            raise ValueError("mixer: True, 'DensityMatrixMixer' or None (other mixers: TeNPy's engines on the mirror)")
+        choice = options.get('mixer', self.use_mixer_by_default)
+        self._mixer_on = choice not in (None, False)
+        if choice not in (None, False, True, self.DefaultMixer):
+            raise ValueError("mixer: True, %r or None (other mixers: TeNPy's engines on the mirror)" % self.DefaultMixer)
         if self._mixer_on and self.shard_matvec:
             raise ValueError("mixer is not available together with shard_matvec")
         self.mixer_activate()
@@ -101,8 +108,8 @@ class TwoSiteDMRGEngine:
     def mixer_activate(self, sweep_activated=None):
         """(Re-)create the mixer from ``mixer_params`` (reference ``Sweep.mixer_activate``)."""
         if self._mixer_on:
-            from .mixer import DensityMatrixMixer
-            self.mixer = DensityMatrixMixer(self.options.get('mixer_params'), self.sweeps if sweep_activated is None else sweep_activated)
+            from . import mixer
+            self.mixer = getattr(mixer, self.DefaultMixer)(self.options.get('mixer_params'), self.sweeps if sweep_activated is None else sweep_activated)
 
     def mixer_cleanup(self):
         """After a sweep: let the amplitude decay; drop the mixer when its time is over (reference ``Sweep.mixer_cleanup``)."""
@@ -148,10 +155,8 @@ class TwoSiteDMRGEngine:
         if gc_was_on:
             gc.disable()
         try:
-            for i0 in range(L - 2):
-                worst = max(worst, self.update_bond(i0, move_right=True).eps)
-            for i0 in range(L - 2, 0, -1):
-                worst = max(worst, self.update_bond(i0, move_right=False).eps)
+            for update in self._sweep_updates():
+                worst = max(worst, update().eps)
         finally:
             if gc_was_on:
                 gc.enable()
@@ -165,6 +170,14 @@ class TwoSiteDMRGEngine:
         st['max_trunc_err'].append(worst)
         st['max_chi'].append(int(np.max(self.psi.chi)))
         return worst
+
+    def _sweep_updates(self):
+        """The updates of one sweep, in order, as calls that return the truncation error: 2 (L - 2) bond updates."""
+        L = self.psi.L
+        for i0 in range(L - 2):
+            yield lambda i0=i0: self.update_bond(i0, move_right=True)
+        for i0 in range(L - 2, 0, -1):
+            yield lambda i0=i0: self.update_bond(i0, move_right=False)
 
     def update_bond(self, i0, move_right=True):
         t0 = time.time()
@@ -268,3 +281,113 @@ class TwoSiteDMRGEngine:
         if phase is not None:
             self.phase_time[phase] += now - self._t_phase
         self._t_phase = now
+
+
+class SingleSiteDMRGEngine(TwoSiteDMRGEngine):
+    """Single-site DMRG for finite chains (reference ``SingleSiteDMRGEngine``, dmrg.py:955-1140, ``combine=False``) with the subspace
+    expansion of ``algorithms/mixer.py`` as its mixer.  The schedule is the reference's ``Sweep.get_sweep_schedule`` for one optimised
+    site: sites 0 .. L - 2 moving right (``LP`` is updated), then L - 1 .. 1 moving left (``RP``).  Per update: the device ``OneSiteH``
+    (its plans handed from visit to visit), ``LanczosGroundState``, ``prepare_svd``, ``mixed_svd``, ``set_B``, the environment.
+
+    Options as for ``TwoSiteDMRGEngine`` with ``mixer``: ``True`` / ``'SubspaceExpansion'`` / ``None``, default ``True`` (the
+    reference's ``use_mixer_by_default``).  While the mixer is on the bond next to the updated site holds a general 2D matrix
+    (S . VH moving right, U . S moving left; the neighbouring tensor stays as it is); without it, 1D singular values.
+    ``shard_matvec`` and ``orthogonal_to`` are not available."""
+    DefaultMixer = 'SubspaceExpansion'
+    use_mixer_by_default = True
+
+    def __init__(self, psi, model_H, options, resume_data=None, orthogonal_to=None):
+        if orthogonal_to:
+            raise ValueError("orthogonal_to is not available for the stand-alone single-site engine")
+        if dict(options).get('shard_matvec', False):
+            raise ValueError("shard_matvec is not available for the stand-alone single-site engine")
+        if psi.L < 2:
+            raise ValueError("single-site DMRG needs at least two sites")
+        super().__init__(psi, model_H, options, resume_data=resume_data)
+
+    def get_sweep_schedule(self):
+        """``(i0, move_right, (update_LP, update_RP))`` of one sweep (reference mps_common.py:438-444 with n = 1)."""
+        L = self.psi.L
+        return [(i0, True, (True, False)) for i0 in range(L - 1)] + [(i0, False, (False, True)) for i0 in range(L - 1, 0, -1)]
+
+    def _sweep_updates(self):
+        for i0, move_right, update_LP_RP in self.get_sweep_schedule():
+            yield lambda a=(i0, move_right, update_LP_RP): self.update_site(*a)
+
+    def prepare_svd(self, theta, move_right):
+        """``theta`` as the matrix of the SVD: the physical leg points away from the direction of the move (reference :978-994)."""
+        if move_right:
+            return theta.combine_legs(['vL', 'p0'], qconj=+1, new_axes=0)
+        return theta.combine_legs(['p0', 'vR'], qconj=-1, new_axes=1)
+
+    def mixed_svd(self, theta, i0, move_right):
+        """``U [(vL.p), vR]``, ``S``, ``VH [vL, (p.vR)]``, ``err`` on the two sites of the bond (reference :996-1110): without a mixer the
+        plain ``svd_theta`` with VH (U) absorbed into the next tensor; with the mixer its decomposition, S . VH (U . S) as the 2D bond
+        matrix and the next tensor unchanged."""
+        psi = self.psi
+        if move_right:
+            nxt = psi.get_B(i0 + 1, form='B').combine_legs(['p', 'vR'], qconj=-1, new_axes=1)
+        else:
+            nxt = psi.get_B(i0 - 1, form='A').combine_legs(['vL', 'p'], qconj=+1, new_axes=0)
+        if self.mixer is None:
+            qtotal = [theta.qtotal, None] if move_right else [None, theta.qtotal]
+            U, S, VH, err, _ = svd_theta(theta, self.trunc_params, qtotal_LR=qtotal, inner_labels=['vR', 'vL'])
+            if move_right:
+                VH = npc.tensordot(VH, nxt, axes=['vR', 'vL'])
+                U.ireplace_label('(vL.p0)', '(vL.p)')
+            else:
+                U = npc.tensordot(nxt, U, axes=['vR', 'vL'])
+                VH.ireplace_label('(p0.vR)', '(p.vR)')
+        else:
+            U, S, VH, err = self.mixer.mix_and_decompose_1site(self, theta, i0, move_right)
+            if move_right:
+                S = npc.tensordot(S, VH, axes=['vR', 'vL']) if isinstance(S, npc.Array) else VH.iscale_axis(S, 'vL')
+                VH = nxt
+                U.ireplace_label('(vL.p0)', '(vL.p)')
+            else:
+                S = npc.tensordot(U, S, axes=['vR', 'vL']) if isinstance(S, npc.Array) else U.iscale_axis(S, 'vR')
+                U = nxt
+                VH.ireplace_label('(p0.vR)', '(p.vR)')
+        return U, S, VH, err
+
+    def update_site(self, i0, move_right, update_LP_RP=None):
+        t0 = time.time()
+        psi, env = self.psi, self.env
+        update_LP, update_RP = update_LP_RP if update_LP_RP is not None else (move_right, not move_right)
+        self._tick(None)
+        eff_H = plain = OneSiteH(env, i0, combine=False, move_right=move_right)
+        cache = self.__dict__.setdefault('_heff_plans', {})
+        if eff_H.factored and cache.get(i0) is not None:      # the plans of this site's previous visit (validated by their keys)
+            eff_H._fplans = cache[i0]
+        plain._expandplans = self.__dict__.setdefault('_expand_plans', {}).setdefault(i0, {})
+        if getattr(self.H, 'explicit_plus_hc', False):
+            eff_H = _plus_hc(eff_H)
+        theta = plain.combine_theta(psi.get_theta(i0, n=1))
+        self.eff_H = plain                                    # (the mixer looks at the plain operator)
+        self._tick('heff')
+        E0, theta, N = LanczosGroundState(eff_H, theta, self.lanczos_params).run()
+        if isinstance(getattr(plain, '_fplans', None), dict) and 'lkey' in plain._fplans:
+            cache[i0] = plain._fplans
+        theta = self.prepare_svd(theta, move_right)
+        self._tick('lanczos')
+        U, S, VH, err = self.mixed_svd(theta, i0, move_right)
+        self._tick('svd')
+        i_L, i_R = (i0, i0 + 1) if move_right else (i0 - 1, i0)
+        psi.set_B(i_L, U.split_legs(['(vL.p)']), form='A')
+        psi.set_B(i_R, VH.split_legs(['(p.vR)']), form='B')
+        psi.set_SR(i_L, S)
+        self._tick('setB')
+        env.invalidate(i_L, i_R, keep_LP=False, keep_RP=False)
+        if update_LP:
+            plain.update_LP(env, i_R, U)
+        if update_RP:
+            plain.update_RP(env, i_L, VH)
+        self._tick('env')
+        us = self.update_stats
+        us['i0'].append(i0)
+        us['E_total'].append(float(E0))
+        us['N_lanczos'].append(N)
+        us['time'].append(time.time() - t0)
+        us['err'].append(err.eps)
+        us['chi'].append(min(S.shape) if isinstance(S, npc.Array) else len(S))
+        return err

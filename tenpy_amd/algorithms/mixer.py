@@ -27,10 +27,10 @@ from ..linalg import _device as dev
 from ..linalg import _herk
 from ..linalg import np_conserved as npc
 from ..linalg.charges import LegPipe
-from ..linalg.truncation import truncate
+from ..linalg.truncation import svd_theta, truncate
 from . import mps_common
 
-stats = {'device_mix_rho': 0, 'declined': 0, 'plans_built': 0, 'why': {}}
+stats = {'device_mix_rho': 0, 'declined': 0, 'plans_built': 0, 'why': {}, 'device_expand': 0, 'expand_declined': 0, 'expand_plans_built': 0}
 
 
 def enabled():
@@ -309,6 +309,163 @@ def generic_mix_rho(eff_H, H, theta, i0, amplitude, mix_left, mix_right, weights
     return rho_L.itranspose(['(vL.p0)', '(vL*.p0*)']), rho_R.itranspose(['(p1.vR)', '(p1*.vR*)'])
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# Subspace expansion of single-site DMRG (reference ``SubspaceExpansion``, mps_common.py:2082-2201).  Moving right the reference
+# decomposes
+#     theta_expand[(vL.p0), (wR.vR)] = LHeff . diag(mix_L on wR) . theta
+# (moving left ``theta . diag(mix_R on wL) . RHeff`` as ``[(vL.wL), (p0.vR)]``) and gets it through ``LHeff``, a scaling pass, a
+# tensordot over the fused leg of length d chi and a ``combine_legs`` copy.  With a factored ``OneSiteH`` the same matrix is
+# ``T1 = LP . theta`` -- a GEMM over chi, the first step of the matvec -- and ONE ``tpa_mpo_expand_batch`` launch that applies W0 entry by
+# entry with the weights multiplied in and writes straight into the charge blocks of the fused matrix (``mps_common.MpoExpandPlan``).
+def expand_enabled():
+    return os.environ.get('TPA_EXPAND_DEVICE', '1') != '0'
+
+
+def _expand_declines(eff_H, H, theta):
+    """Why the device route of the subspace expansion does not take this call (counted in ``stats['why']``), or ``None``."""
+    if not expand_enabled():
+        return 'switched off'
+    if not ((type(eff_H) is mps_common.OneSiteH or (isinstance(eff_H, mps_common.OneSiteH) and
+                                                    getattr(type(eff_H), '_reference_class', None) is not None))
+            and getattr(eff_H, 'factored', False)):
+        return 'operator'
+    if getattr(H, 'explicit_plus_hc', False):        # (the stacked form with the adjoint part: the generic route serves it)
+        return 'explicit_plus_hc'
+    if not getattr(H, 'finite', True):
+        return 'infinite'
+    if not dev.lib_provides('tpa_mpo_expand_batch'):      # an emulation that predates the entry point: never forwarded to the real library
+        return 'entry point'
+    env = getattr(eff_H, '_env', None)
+    if env is not None and getattr(env, 'bra', None) is not getattr(env, 'ket', None):
+        return 'bra is not ket'
+    if len({np.dtype(t.dtype) for t in (theta, eff_H.LP, eff_H.RP, eff_H.W0)}) != 1:
+        return 'mixed dtypes'
+    if np.any(eff_H.LP.qtotal != 0) or np.any(eff_H.RP.qtotal != 0):
+        return 'charged environment'
+    if theta.stored_blocks == 0:
+        return 'empty theta'
+    return None
+
+
+def _expand_weights(H, i0, amplitude, move_right, weights):
+    """``(mix, Id, proj)`` on the outgoing MPO bond leg of site ``i0``: the weights (``mix_L`` of the bond to the right, moving right;
+    ``mix_R`` of the bond to the left), the index whose slice is the unperturbed theta and -- that index is ``None``: the stacked form
+    -- the mask of the indices that stay next to theta itself.  ``amplitude`` as the mixer holds it: the weights carry its root, so
+    that it means the same for both mixers (reference :2134-2138)."""
+    bond = i0 if move_right else i0 - 1
+    mix_L, mix_R, IdL, IdR = weights if weights is not None else mix_weights(H, bond, np.sqrt(amplitude))
+    mix, Id = (mix_L, IdL) if move_right else (mix_R, IdR)
+    proj = None
+    if Id is None:
+        proj = np.ones(len(mix), bool)
+        for k in (IdL, IdR):
+            if k is not None:
+                proj[k] = False
+        mix = np.full(len(mix), float(np.sqrt(amplitude)))
+    return np.asarray(mix, np.float64), Id, proj
+
+
+def device_expand_1site(eff_H, H, theta, i0, amplitude, move_right, weights=None):
+    """``(theta_expand, Id)``: the matrix that ``SubspaceExpansion.mix_and_decompose_1site`` hands to ``svd_theta``, with the legs and
+    labels of the reference after its ``combine_legs`` -- ``['(vL.p0)', '(wR.vR)']`` moving right, ``['(vL.wL)', '(p0.vR)']`` moving
+    left -- and the index of the outgoing MPO bond leg whose slice is the unperturbed theta (0 in the stacked form); or ``None``
+    where the route declines (``_expand_declines``).  ``theta``: ``[vL, p0, vR]``, or prepared for the SVD as ``[(vL.p0), vR]`` /
+    ``[vL, (p0.vR)]`` -- its pipe is then the pipe of the result.  ``weights``: ``(mix_L, mix_R, IdL, IdR)`` in place of
+    ``mix_weights(H, bond, sqrt(amplitude))``."""
+    why = _expand_declines(eff_H, H, theta)
+    if why is not None:
+        stats['expand_declined'] += 1
+        stats['why'][why] = stats['why'].get(why, 0) + 1
+        return None
+    mix, Id, proj = _expand_weights(H, i0, amplitude, move_right, weights)
+    pipe = None
+    if theta.rank == 2:
+        want = ['(vL.p0)', 'vR'] if move_right else ['vL', '(p0.vR)']
+        theta = theta if list(theta.get_leg_labels()) == want else theta.transpose(want)
+        pipe = theta.legs[0 if move_right else 1]
+        theta = theta.split_legs()
+    th3 = eff_H.combine_theta(theta)                                            # vL, p0, vR
+    if move_right:          # vR*, wR, p0, vR (contracted index: chi, not d chi): the first GEMM of the matvec, by its cached plan p1
+        fp = eff_H._plans(th3)
+        T1 = fp['p1'].apply(eff_H._LPf, th3) if fp is not None else npc.tensordot(eff_H._LPf, th3, axes=['vR', 'vL'])
+    else:                   # vL, p0, wL, vL* (the matvec has no such step: the plan cache of `tensordot`)
+        T1 = npc.tensordot(th3, eff_H._RPf, axes=['vR', 'vL'])
+    handover = (th3._struct_key(), eff_H.LP._struct_key(), eff_H.RP._struct_key(), eff_H.W0._struct_key(), bool(move_right),
+                (mix == 0).tobytes(), None if proj is None else proj.tobytes(), None if pipe is None else pipe._content_key())
+    cache = eff_H.__dict__.setdefault('_expandplans', {})
+    plan = cache.get(move_right)
+    if plan is None or plan.handover != handover or plan.dtype != np.dtype(T1.dtype):
+        try:
+            plan = mps_common.MpoExpandPlan.get(T1, eff_H.W0, move_right, mix == 0, proj, th3 if proj is not None else None, pipe)
+        except mps_common.ExpandJobLimit:
+            stats['expand_declined'] += 1
+            stats['why']['too many jobs'] = stats['why'].get('too many jobs', 0) + 1
+            return None
+        if getattr(plan, 'handover', None) is None:
+            stats['expand_plans_built'] += 1
+        plan.handover = handover
+        cache[move_right] = plan
+    res = plan.apply(T1, mix, th3 if proj is not None else None)
+    stats['device_expand'] += 1
+    return res, (0 if proj is not None else Id)
+
+
+def _heff_1site(eff_H, left):
+    """``LHeff [(vR*.p0), wR, (vR.p0*)]`` / ``RHeff [(p0*.vL), wL, (p0.vL*)]`` of a one-site operator (the reference's
+    ``_get_LHeff`` / ``_get_RHeff``, on site ``i0`` with the labels of ``p0``)."""
+    W = eff_H.W0
+    if left:
+        H = npc.tensordot(eff_H.LP, W, axes=['wR', 'wL'])
+        H = H.combine_legs([['vR*', 'p0'], ['vR', 'p0*']], qconj=[+1, -1])
+        return H.transpose(['(vR*.p0)', 'wR', '(vR.p0*)'])
+    H = npc.tensordot(W, eff_H.RP, axes=['wR', 'wL'])
+    H = H.combine_legs([['p0*', 'vL'], ['p0', 'vL*']], qconj=[+1, -1])
+    return H.transpose(['(p0*.vL)', 'wL', '(p0.vL*)'])
+
+
+def generic_expand_1site(eff_H, H, theta, i0, amplitude, move_right, weights=None):
+    """The same ``(theta_expand, Id)`` by the reference's statements (:2140-2164, :2170-2194) through ``LHeff`` / ``RHeff``: what
+    ``SubspaceExpansion`` issues where ``device_expand_1site`` declines, and the in-process comparison of the tests.  The stacked form
+    moving left is written as the mirror image of the one moving right -- the reference's lines name the leg ``wR`` there and leave
+    the amplitude out -- and ``explicit_plus_hc`` adds the adjoint part as the reference does."""
+    bond = i0 if move_right else i0 - 1
+    mix_L, mix_R, IdL, IdR = weights if weights is not None else mix_weights(H, bond, np.sqrt(amplitude))
+    plus_hc = bool(getattr(H, 'explicit_plus_hc', False))
+    if theta.rank != 2:
+        theta = theta.combine_legs(['vL', 'p0'], qconj=+1, new_axes=0) if move_right else theta.combine_legs(['p0', 'vR'], qconj=-1, new_axes=1)
+    w, Id = ('wR', IdL) if move_right else ('wL', IdR)
+    Heff = _heff_1site(eff_H, move_right)
+
+    def dot(Heff_, th):
+        if move_right:
+            return npc.tensordot(Heff_, th, axes=['(vR.p0*)', '(vL.p0)']).ireplace_label('(vR*.p0)', '(vL.p0)')
+        return npc.tensordot(th, Heff_, axes=['(p0.vR)', '(p0*.vL)']).ireplace_label('(p0.vL*)', '(p0.vR)')
+    if not plus_hc and Id is not None:
+        expand = dot(Heff.iscale_axis(mix_L if move_right else mix_R, w), theta)
+    else:
+        wleg = Heff.get_leg(w)
+        stack = [theta.add_trivial_leg(1, w, wleg.qconj)]          # theta itself
+        proj = np.ones(wleg.ind_len, bool)
+        for k in (IdL, IdR):
+            if k is not None:
+                proj[k] = False
+        Heff.iproject(proj, w)
+        Heff = Heff * np.sqrt(amplitude)
+        stack.append(dot(Heff, theta))
+        if plus_hc:         # (Heff^dagger theta) = conj(Heff^T conj(theta))
+            if move_right:
+                th = npc.tensordot(Heff, theta.conj(), axes=['(vR*.p0)', '(vL*.p0*)'])
+                stack.append(th.itranspose(['(vR.p0*)', 'wR', 'vR*']).iconj())
+            else:
+                th = npc.tensordot(theta.conj(), Heff, axes=['(p0*.vR*)', '(p0.vL*)'])
+                stack.append(th.itranspose(['vL*', 'wL', '(p0*.vL)']).iconj())
+        expand = npc.concatenate(stack, axis=w)
+        Id = 0
+    if move_right:
+        return expand.combine_legs(['wR', 'vR'], qconj=-1), Id
+    return expand.combine_legs(['vL', 'wL'], qconj=+1), Id
+
+
 class DensityMatrixMixer:
     """The density-matrix mixer of two-site DMRG for the stand-alone driver, with the reference's options and semantics
     (``Mixer`` :1617-1653, ``DensityMatrixMixer`` :1962-2079): ``amplitude`` (1e-5), ``decay`` (2: the amplitude is divided by it after
@@ -388,3 +545,50 @@ class DensityMatrixMixer:
         S /= S.norm()
         assert np.all(S.qtotal == 0)
         return U, S, VH, err_L + err_R, S_a[keep_L]
+
+
+def decompose_expanded(theta_expand, Id, theta, trunc_params, move_right, svd_theta=svd_theta):
+    """``svd_theta`` of the expanded matrix with the total charge of ``theta`` on the side of the site, then the slice ``Id`` of the
+    outgoing MPO bond leg of VH (U): ``U S VH`` is the truncated ``theta`` (reference :2164-2169, :2194-2199).  ``svd_theta``: the
+    module form passes the reference's own."""
+    if move_right:
+        U, S, VH, err, _ = svd_theta(theta_expand, trunc_params, qtotal_LR=[theta.qtotal, None], inner_labels=['vR', 'vL'])
+        VH = VH.split_legs('(wR.vR)').take_slice(Id, 'wR')
+    else:
+        U, S, VH, err, _ = svd_theta(theta_expand, trunc_params, qtotal_LR=[None, theta.qtotal], inner_labels=['vR', 'vL'])
+        U = U.split_legs('(vL.wL)').take_slice(Id, 'wL')
+    return U, S, VH, err
+
+
+class SubspaceExpansion:
+    """The subspace expansion of single-site DMRG for the stand-alone driver, with the reference's options and semantics (``Mixer``
+    :1617-1653, ``SubspaceExpansion`` :2082-2201): ``amplitude`` (1e-5), ``decay`` (2), ``disable_after`` (15).  The expanded matrix
+    comes from ``device_expand_1site`` -- one GEMM over chi and one ``tpa_mpo_expand_batch`` launch -- or, where that declines, from
+    the reference's statements (``generic_expand_1site``); the decomposition is the reference's."""
+    can_decompose_1site = True
+
+    def __init__(self, options=None, sweep_activated=0):
+        options = dict(options or {})
+        self.amplitude = options.get('amplitude', 1.e-5)
+        self.decay = options.get('decay', 2.)
+        self.disable_after = options.get('disable_after', 15)
+        assert self.decay is None or self.decay >= 1.
+        assert self.disable_after is None or self.disable_after > 0
+        assert self.amplitude <= 1.
+        self.sweep_activated = sweep_activated
+
+    update_amplitude = DensityMatrixMixer.update_amplitude
+
+    def expand(self, engine, theta, i0, move_right):
+        """``(theta_expand, Id)`` on the device route, else by the reference's statements."""
+        eff_H = engine.eff_H
+        got = device_expand_1site(eff_H, engine.env.H, theta, i0, self.amplitude, move_right)
+        if got is None:
+            got = generic_expand_1site(eff_H, engine.env.H, theta, i0, self.amplitude, move_right)
+        return got
+
+    def mix_and_decompose_1site(self, engine, theta, i0, move_right):
+        """``(U, S, VH, err)`` of the expanded ``theta`` (prepared for the SVD: ``[(vL.p0), vR]`` moving right, ``[vL, (p0.vR)]`` moving
+        left), projected back such that ``U S VH`` is the truncated ``theta`` (reference :2164-2169, :2194-2199)."""
+        theta_expand, Id = self.expand(engine, theta, i0, move_right)
+        return decompose_expanded(theta_expand, Id, theta, engine.trunc_params, move_right)

@@ -37,7 +37,8 @@ from ..linalg import np_conserved as npc
 from ..linalg.charges import DipolarChargeInfo
 from . import mps_common as dev_mc
 
-__all__ = ['device_two_site_h', 'device_one_site_h', 'device_zero_site_h', 'device_sum_operator', 'hinted_mixed_svd', 'device_mixer_mix_rho']
+__all__ = ['device_two_site_h', 'device_one_site_h', 'device_zero_site_h', 'device_sum_operator', 'hinted_mixed_svd', 'device_mixer_mix_rho',
+           'device_subspace_expansion']
 
 # Smallest "largest bond sector" for which the device form is used.  Round 3 measurement (module form on the MI355X, Heisenberg
 # L = 100, mixer ramp): with the reference's own class below 64 -- four generic tensordots with transposed copies per matvec,
@@ -52,7 +53,10 @@ stats = {'device': 0, 'reference': 0,      # bonds handled by the device form / 
          # `plus_hc_other`: sums of anything but a device operator and its own adjoint (the reference's class, unchanged)
          'plus_hc_device': 0, 'plus_hc_declined': 0, 'plus_hc_reference': 0, 'plus_hc_other': 0,
          # DensityMatrixMixer.mix_rho: calls served by `mixer.device_mix_rho` (one tpa_herk_chain launch per side) / by the reference's statements
-         'mixer_device': 0, 'mixer_reference': 0}
+         'mixer_device': 0, 'mixer_reference': 0,
+         # SubspaceExpansion.mix_and_decompose_1site: expansions served by `mixer.device_expand_1site` (one tpa_mpo_expand_batch launch) / by
+         # the reference's method
+         'expand_device': 0, 'expand_reference': 0}
 
 
 def device_two_site_h(Ref):
@@ -175,10 +179,15 @@ def device_sum_operator(Ref):
     return DeviceSumOperator
 
 
-def device_one_site_h(Ref):
+def device_one_site_h(Ref, boundary_envs=False):
+    """``boundary_envs`` (the class bound for single-site DMRG): an environment whose legs all have 1-wide blocks -- the reference's
+    ``init_LP`` / ``init_RP`` of a finite chain, which puts the bra leg before the ket leg on the right -- is taken with its legs
+    relabelled in the order of the factored forms (a view, no copy) instead of being handed back to the reference's class; the last
+    site of every right sweep is such a site."""
     class DeviceOneSiteH(dev_mc.OneSiteH):
         __doc__ = "Device form of tenpy.algorithms.mps_common.OneSiteH (see tenpy_amd/algorithms/module_form.py)."
         _reference_class = Ref
+        _boundary_envs = boundary_envs
 
         def __new__(cls, env, i0, combine=False, move_right=True):
             tensors = cls._device_tensors(env, i0, combine)
@@ -197,6 +206,8 @@ def device_one_site_h(Ref):
             if combine or not _plain_env(env):
                 return None
             LP, W0, RP = env.get_LP(i0), env.H.get_W(i0), env.get_RP(i0)
+            if boundary_envs:
+                LP, RP = _boundary_view(LP, ['vR*', 'wR', 'vR']), _boundary_view(RP, ['wL', 'vL', 'vL*'])
             if list(W0.get_leg_labels()) != ['wL', 'wR', 'p', 'p*'] or dev_mc._factored_plan_class(LP, RP, W0) is None:
                 return None
             return LP, W0, RP
@@ -211,6 +222,14 @@ def device_one_site_h(Ref):
 
     DeviceOneSiteH.__name__ = DeviceOneSiteH.__qualname__ = 'OneSiteH'
     return DeviceOneSiteH
+
+
+def _boundary_view(A, labels):
+    """``A`` with its legs in the order ``labels`` where that moves no data (every leg has 1-wide blocks), else ``A`` itself."""
+    have = list(A.get_leg_labels())
+    if have == labels or sorted(have) != sorted(labels) or not all(np.all(leg.get_block_sizes() == 1) for leg in A.legs):
+        return A
+    return dev_mc._relabel_view(A, labels)
 
 
 def device_zero_site_h(Ref):
@@ -274,6 +293,27 @@ def device_mixer_mix_rho(ref_mix_rho):
     mix_rho.__doc__ = ref_mix_rho.__doc__
     mix_rho._tpa_wrapped = True
     return mix_rho
+
+
+def device_subspace_expansion(ref_method, ref_mc):
+    """Wraps ``SubspaceExpansion.mix_and_decompose_1site`` (mps_common.py:2133-2201) IN PLACE, like ``device_mixer_mix_rho``: with a device
+    ``OneSiteH`` as ``engine.eff_H``, and where ``mixer.device_expand_1site`` does not decline, ``theta_expand`` comes from the device
+    route -- ``LHeff`` / ``RHeff`` are not built -- and is decomposed by the statements of ``mixer.SubspaceExpansion`` with the
+    reference's own ``svd_theta``; otherwise the reference's method runs."""
+    from . import mixer as dev_mixer
+
+    def mix_and_decompose_1site(self, engine, theta, i0, move_right):
+        eff_H = getattr(engine, 'eff_H', None)
+        if isinstance(eff_H, dev_mc.OneSiteH) and getattr(eff_H, 'i0', None) == i0:
+            got = dev_mixer.device_expand_1site(eff_H, engine.env.H, theta, i0, self.amplitude, move_right)
+            if got is not None:
+                stats['expand_device'] += 1
+                return dev_mixer.decompose_expanded(got[0], got[1], theta, engine.trunc_params, move_right, svd_theta=ref_mc.svd_theta)
+        stats['expand_reference'] += 1
+        return ref_method(self, engine, theta, i0, move_right)
+    mix_and_decompose_1site.__doc__ = ref_method.__doc__
+    mix_and_decompose_1site._tpa_wrapped = True
+    return mix_and_decompose_1site
 
 
 def batched_tebd_evolve_step(ref_tebd):

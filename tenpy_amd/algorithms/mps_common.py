@@ -586,6 +586,23 @@ def _leg_block_pos(leg, idx):
     return b, idx - sl[b]
 
 
+def _join_entries_blocks(X, mid, b_in, n_entries):
+    """All (block of X, entry of W) pairs whose in-blocks agree on the legs ``mid`` of X -- ``b_in[a]``: the block of every entry on leg
+    ``a`` --: a sorted join on the combined block number of these legs.  Returns the block and the entry of every pair, ordered by
+    block, the entries of a block in table order."""
+    xq = X._qdata
+    key_e, key_x = np.zeros(n_entries, dtype=np.int64), np.zeros(len(xq), dtype=np.int64)
+    for a in mid:
+        n = X.legs[a].block_number
+        key_e, key_x = key_e * n + b_in[a], key_x * n + xq[:, a]
+    oe = np.argsort(key_e, kind='stable')
+    lo, hi = np.searchsorted(key_e[oe], key_x, side='left'), np.searchsorted(key_e[oe], key_x, side='right')
+    cnt = hi - lo
+    ib = np.repeat(np.arange(len(xq)), cnt)
+    ie = oe[np.arange(len(ib)) - np.repeat(np.cumsum(cnt) - cnt, cnt) + np.repeat(lo, cnt)]
+    return ib, ie
+
+
 class MpoEntryApplyPlan(_MpoStepPlan):
     """``MpoApplyPlan`` for MPO tensors of any block structure -- MPO bond legs with blocks wider than 1, physical sectors wider than
     ``TPA_MPO_APPLY_MAXD``, no conserved charge -- entry by entry.  X has its two virtual legs first and last and the MPO and physical
@@ -629,17 +646,8 @@ class MpoEntryApplyPlan(_MpoStepPlan):
         for n, a in enumerate(xa):
             b_in[a], pos_in[a] = _leg_block_pos(X.legs[a], keys[:, col_in[n]])
             b_out[a], pos_out[a] = _leg_block_pos(legs[a], keys[:, col_out[n]])
-        # all (block of X, entry) pairs whose in-blocks agree: a sorted join on the combined block number of the middle legs
         xq = X._qdata
-        nb = [X.legs[a].block_number for a in mid]
-        key_e, key_x = np.zeros(len(keys), dtype=np.int64), np.zeros(len(xq), dtype=np.int64)
-        for a, n in zip(mid, nb):
-            key_e, key_x = key_e * n + b_in[a], key_x * n + xq[:, a]
-        oe = np.argsort(key_e, kind='stable')
-        lo, hi = np.searchsorted(key_e[oe], key_x, side='left'), np.searchsorted(key_e[oe], key_x, side='right')
-        cnt = hi - lo
-        ib = np.repeat(np.arange(len(xq)), cnt)
-        ie = oe[np.arange(len(ib)) - np.repeat(np.cumsum(cnt) - cnt, cnt) + np.repeat(lo, cnt)]
+        ib, ie = _join_entries_blocks(X, mid, b_in, len(keys))
         self.empty = len(ib) == 0
         if self.empty:
             return
@@ -699,6 +707,207 @@ class MpoEntryApplyPlan(_MpoStepPlan):
         """The row of a ``tpa_lanczos_run`` program that applies this plan from slot ``a_slot`` into slot ``c_slot`` (kind 6)."""
         return [6, 0, self.jobs_dev.data_ptr(), self.rows_dev.data_ptr(), self.terms_dev.data_ptr(), self.n_jobs, a_slot, 0, c_slot,
                 self.max_cols, 0, 0]
+
+
+class ExpandJobLimit(ValueError):
+    """The expanded matrix has more cells than one ``tpa_mpo_expand_batch`` launch takes jobs."""
+
+
+class MpoExpandPlan(_MpoStepPlan):
+    """The matrix that the subspace expansion of single-site DMRG decomposes (reference ``SubspaceExpansion.mix_and_decompose_1site``,
+    mps_common.py:2140-2164 and :2170-2194), written in ONE ``tpa_mpo_expand_batch`` launch from ``T1 = LP . theta`` (right move,
+    legs ``vR*, wR, p0, vR``) or ``T1 = theta . RP`` (left move, legs ``vL, p0, wL, vL*``):
+
+        right:  E[(vL.p0), (wR.vR)] = sum_{w, p*} mix[wR] W[w, wR, p0, p*] T1[vL, w, p*, vR]
+        left :  E[(vL.wL), (p0.vR)] = sum_{w, p*} mix[wL] W[wL, w, p0, p*] T1[vL, p*, w, vR]
+
+    entry by entry of W (``_mpo_coo``: every block structure of the MPO is served by the one form), straight into the charge blocks of
+    the fused matrix: ``LHeff`` / ``RHeff``, the scaling pass and the ``combine_legs`` copy do not happen.  A job is one cell -- the
+    slice of an incoming block pair of the row pipe times that of the column pipe -- of a stored charge block; a block is stored when
+    one of its cells receives a term (whatever the weights: a sector that ``mix = 0`` wipes out holds zeros, as after the reference's
+    ``iscale_axis``), every cell of a stored block is covered, and cells or rows without terms are written as zeros.
+
+    ``move_right``: the direction.  ``zero``: bool per index of the outgoing MPO bond leg, True where the weight is exactly zero -- the
+    terms of these rows are not read.  ``proj`` (with ``theta``, legs ``vL, p0, vR``): the stacked form of ``IdL`` / ``IdR`` = ``None``
+    (:2146-2163 without the ``explicit_plus_hc`` part) -- the outgoing MPO leg is one trivial index, whose rows copy ``theta`` itself
+    (the second source of the kernel), followed by the indices with ``proj`` True.  The weights are multiplied into the coefficients
+    on the host when the plan is applied (one rounding each)."""
+    _cache = {}
+    _table = staticmethod(_mpo_coo)
+    MAX_JOBS = 60000        # (the entry point takes 65535; the margin of the sibling plans)
+
+    @classmethod
+    def get(cls, X, W, move_right, zero, proj=None, theta=None, row_pipe=None):
+        """Cached constructor: the plan depends on the block structure and the leg charges of ``X`` (and ``theta``), on the MPO tensor,
+        the direction and the two masks."""
+        t1 = cls._table(W)
+        key = (X._struct_key(), str(X.dtype), id(t1), bool(move_right), np.asarray(zero, bool).tobytes(),
+               None if proj is None else np.asarray(proj, bool).tobytes(), None if theta is None else theta._struct_key(),
+               X.qtotal.tobytes(), tuple((l.charges.tobytes(), int(l.qconj)) for l in X.legs),
+               None if row_pipe is None else row_pipe._content_key())
+        plan = cls._cache.get(key)
+        if plan is None or plan._tables_alive[0] is not t1:
+            if len(cls._cache) > 4096:
+                cls._cache.clear()
+            plan = cls._cache[key] = cls(X, W, move_right, zero, proj, theta, row_pipe)
+            plan._tables_alive = (t1, None)       # (the key holds its id(): see `_MpoStepPlan.get`)
+        return plan
+
+    def __init__(self, X, W, move_right, zero, proj=None, theta=None, row_pipe=None):
+        from ..linalg.charges import LegCharge, LegPipe
+        w_in, w_out = ('wL', 'wR') if move_right else ('wR', 'wL')
+        want = ['vR*', 'wR', 'p0', 'vR'] if move_right else ['vL', 'p0', 'wL', 'vL*']
+        assert list(X.get_leg_labels()) == want and list(W.get_leg_labels()) == ['wL', 'wR', 'p0', 'p0*']
+        ax_w, ax_p = (1, 2) if move_right else (2, 1)
+        keys, vals = MpoEntryApplyPlan._entries(W, w_in, w_out, 'p0', 'p0*')      # (w_in, w_out, p_out, p_in)
+        wleg, pleg = W.get_leg(w_out), W.get_leg('p0')
+        zero = np.asarray(zero, bool)
+        assert zero.shape == (wleg.ind_len,)
+        w_new = keys[:, 1]
+        self.stacked = proj is not None
+        if self.stacked:       # the outgoing leg: [theta itself] + [the indices that survive the projection]
+            proj = np.asarray(proj, bool)
+            assert proj.shape == (wleg.ind_len,) and theta is not None and list(theta.get_leg_labels()) == ['vL', 'p0', 'vR']
+            assert np.all(W.qtotal == 0), "the stacked form puts theta next to W . theta: they must carry the same charge"
+            _, _, kept = wleg.project(proj)
+            sizes = np.concatenate([[1], kept.get_block_sizes()])
+            charges = np.concatenate([np.zeros((1, W.chinfo.qnumber), dtype=kept.charges.dtype), kept.charges], axis=0)
+            wleg = LegCharge.from_qind(W.chinfo, np.append([0], np.cumsum(sizes)), charges, wleg.qconj)
+            new_of_old = np.where(proj, np.cumsum(proj), -1)
+            keep = new_of_old[keys[:, 1]] >= 0
+            keys, vals = keys[keep], vals[keep]
+            w_new = new_of_old[keys[:, 1]]
+        self.dtype = np.result_type(X.dtype, W.dtype)
+        self.qtotal = X.chinfo.make_valid(X.qtotal + W.qtotal)
+        if move_right:
+            self.row_pipe = row_pipe if row_pipe is not None else LegPipe([X.legs[0], pleg], qconj=+1)
+            self.col_pipe = LegPipe([wleg, X.legs[3]], qconj=-1)
+            self.labels = ['(vL.p0)', '(wR.vR)']
+        else:
+            self.row_pipe = LegPipe([X.legs[0], wleg], qconj=+1)
+            self.col_pipe = row_pipe if row_pipe is not None else LegPipe([pleg, X.legs[3]], qconj=-1)     # (the given pipe of theta)
+            self.labels = ['(vL.wL)', '(p0.vR)']
+        self.legs = [self.row_pipe, self.col_pipe]
+        self.w_leg = wleg
+        # ---- all (block of T1, entry of W) pairs: the join of `MpoEntryApplyPlan`
+        xq = X._qdata
+        b_in, pos_in = {}, {}
+        b_in[ax_w], pos_in[ax_w] = _leg_block_pos(X.legs[ax_w], keys[:, 0])
+        b_in[ax_p], pos_in[ax_p] = _leg_block_pos(X.legs[ax_p], keys[:, 3])
+        ib, ie = _join_entries_blocks(X, [1, 2], b_in, len(keys))
+        bw, pw = _leg_block_pos(wleg, w_new)
+        bp, pp = _leg_block_pos(pleg, keys[:, 2])
+        shapes_x = X._block_shapes()
+        post_x = shapes_x[ib, 3]
+        # per pair: blocks and positions on the four legs of the result, the source row, the value and the (old) outgoing index
+        pr = dict(v0=xq[ib, 0], v1=xq[ib, 3], bw=bw[ie], pw=pw[ie], bp=bp[ie], pp=pp[ie],
+                  off=X._offsets[ib] + (pos_in[1][ie] * shapes_x[ib, 2] + pos_in[2][ie]) * post_x,
+                  ld=shapes_x[ib, 1] * shapes_x[ib, 2] * post_x, val=vals[ie].astype(np.complex128), w=keys[ie, 1],
+                  sel=np.zeros(len(ib), np.int64))
+        if self.stacked and theta.stored_blocks:       # the rows of theta: one term each, alpha = 1, read from the second source
+            tq, ts = theta._qdata, theta._block_shapes()
+            tb = np.repeat(np.arange(len(tq)), ts[:, 1])
+            tp = np.arange(len(tb)) - np.repeat(np.cumsum(ts[:, 1]) - ts[:, 1], ts[:, 1])
+            z = np.zeros(len(tb), np.int64)
+            th = dict(v0=tq[tb, 0], v1=tq[tb, 2], bw=z, pw=z, bp=tq[tb, 1], pp=tp, off=theta._offsets[tb] + tp * ts[tb, 2],
+                      ld=ts[tb, 1] * ts[tb, 2], val=np.ones(len(tb), np.complex128), w=z - 1, sel=z + 1)
+            pr = {k: np.concatenate([pr[k], th[k]]) for k in pr}
+            self.theta_key = theta._struct_key()
+        self.empty = len(pr['off']) == 0
+        if self.empty:
+            return
+        # ---- cells and charge blocks
+        qr, qc = self.row_pipe.q_map, self.col_pipe.q_map
+        if move_right:      # rows (vL, p0), columns (wR, vR)
+            rc = self.row_pipe._map_incoming_qind(np.stack([pr['v0'], pr['bp']], axis=1))
+            cc = self.col_pipe._map_incoming_qind(np.stack([pr['bw'], pr['v1']], axis=1))
+            pos_r, pos_c = pr['pp'], pr['pw']
+        else:               # rows (vL, wL), columns (p0, vR)
+            rc = self.row_pipe._map_incoming_qind(np.stack([pr['v0'], pr['bw']], axis=1))
+            cc = self.col_pipe._map_incoming_qind(np.stack([pr['bp'], pr['v1']], axis=1))
+            pos_r, pos_c = pr['pw'], pr['pp']
+        blk, sizes = self._rank_blocks(np.stack([qr[rc, 2], qc[cc, 2]], axis=1))
+        ld_blk = self.col_pipe.get_block_sizes()[self.qdata[:, 1]]
+        # one job per cell of a stored block
+        jk, jr, jc = [], [], []
+        for k, (Qr, Qc) in enumerate(self.qdata.tolist()):
+            r_cells, c_cells = np.nonzero(qr[:, 2] == Qr)[0], np.nonzero(qc[:, 2] == Qc)[0]
+            jk.append(np.full(len(r_cells) * len(c_cells), k))
+            jr.append(np.repeat(r_cells, len(c_cells)))
+            jc.append(np.tile(c_cells, len(r_cells)))
+        jk, jr, jc = np.concatenate(jk), np.concatenate(jr), np.concatenate(jc)
+        bs_r = [np.asarray(l.get_block_sizes(), dtype=np.int64) for l in self.row_pipe.legs]
+        bs_c = [np.asarray(l.get_block_sizes(), dtype=np.int64) for l in self.col_pipe.legs]
+        pre, n_r = bs_r[0][qr[jr, 3]], bs_r[1][qr[jr, 4]]
+        n_c, post = bs_c[0][qc[jc, 3]], bs_c[1][qc[jc, 4]]
+        ld = ld_blk[jk]
+        n_rows = n_r * n_c
+        row_begin = np.cumsum(n_rows) - n_rows
+        jobs = np.zeros((len(jk), 8), dtype=np.int64)
+        jobs[:, 0], jobs[:, 1], jobs[:, 2], jobs[:, 3] = self.offsets[jk] + qr[jr, 0] * ld, pre, n_rows, post
+        jobs[:, 4], jobs[:, 5] = row_begin, n_r * ld
+        if len(jobs) > self.MAX_JOBS:       # (one job per blockIdx.y; the caller takes the generic route)
+            raise ExpandJobLimit("%d cells for one tpa_mpo_expand_batch launch" % len(jobs))
+        assert int(np.sum(pre * n_rows * post)) == self.total
+        # rows of a job: (position on the inner leg of the row pipe, position on the outer leg of the column pipe)
+        rj = np.repeat(np.arange(len(jk)), n_rows)
+        ro = np.arange(len(rj)) - row_begin[rj]
+        rows = np.zeros((len(rj), 4), dtype=np.int64)
+        rows[:, 2] = (ro // n_c[rj]) * ld[rj] + qc[jc[rj], 0] + (ro % n_c[rj]) * post[rj]
+        # the job of every pair, then its row; terms grouped by row, in the order of the pairs
+        n_cc = len(qc)
+        cell_key = jr * n_cc + jc
+        order = np.argsort(cell_key)
+        job_of = order[np.searchsorted(cell_key[order], rc * n_cc + cc)]
+        assert np.array_equal(cell_key[job_of], rc * n_cc + cc) and np.array_equal(jk[job_of], blk)
+        assert np.array_equal(pre[job_of[:len(ib)]], shapes_x[ib, 0]) and np.array_equal(post[job_of[:len(ib)]], post_x)
+        row = row_begin[job_of] + pos_r * n_c[job_of] + pos_c
+        rows[row, 3] = pr['sel']
+        live = ~zero[np.maximum(pr['w'], 0)] | (pr['w'] < 0)        # (rows of a zero weight: no terms, zeros are written)
+        key = np.lexsort((np.arange(len(row)), row))
+        key = key[live[key]]
+        counts = np.bincount(row[key], minlength=len(rows)).astype(np.int64)
+        rows[:, 0], rows[:, 1] = np.cumsum(counts) - counts, counts
+        assert np.all(counts[rows[:, 3] == 1] == 1), "a row of theta has exactly one term"
+        terms = np.zeros((max(len(key), 1), 4), dtype=np.int64)
+        terms[:len(key), 0], terms[:len(key), 1] = pr['off'][key], pr['ld'][key]
+        self.term_val, self.term_w = pr['val'][key], pr['w'][key]
+        if self.dtype.kind != 'c':
+            assert np.all(self.term_val.imag == 0)
+        self.jobs_host, self.rows_host, self.terms_host, self.sizes = jobs, rows, terms, sizes
+        self.jobs_dev, self.rows_dev = dev.to_device(jobs), dev.to_device(rows)
+        self.terms_dev = self._mix_host = None
+        self.n_jobs, self.max_cols = len(jobs), int(np.max(pre * post))
+        self.x_key = X._struct_key()
+        cols_t = (pre * post)[job_of[key]]
+        self.bytes = 8 * (2 if self.dtype.kind == 'c' else 1) * int(np.sum(cols_t) + np.sum((pre * post)[rj]))
+        self.flops = (8 if self.dtype.kind == 'c' else 2) * int(np.sum(cols_t))
+
+    def _set_weights(self, mix):
+        """alpha = fl(mix[outgoing index] * W entry), 1 for the rows of theta; uploaded once per bond and amplitude."""
+        mix = np.ascontiguousarray(mix, np.float64)
+        if self._mix_host is None or not np.array_equal(self._mix_host, mix):
+            alpha = np.where(self.term_w >= 0, mix[np.maximum(self.term_w, 0)] * self.term_val, self.term_val)
+            _pack_alpha(self.terms_host[:len(alpha)], alpha)
+            self.terms_dev, self._mix_host = dev.to_device(self.terms_host), mix.copy()
+
+    def apply(self, X, mix, theta=None):
+        """The expanded matrix as a new Array.  ``mix``: the real weight of every index of the outgoing MPO bond leg of W (the stacked
+        form reads it at the indices it keeps)."""
+        res = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
+        if self.empty:
+            return res
+        assert X._struct_key() == self.x_key and X.dtype == self.dtype
+        src2 = None
+        if self.stacked:
+            assert theta is not None and theta.dtype == self.dtype and theta._struct_key() == self.theta_key
+            src2 = theta._arena.data_ptr()
+        self._set_weights(mix)
+        res._set_blocks(self.qdata, arena=dev.empty(self.total, self.dtype), qdata_sorted=True)
+        dev.check(dev.lib().tpa_mpo_expand_batch(dev.code(self.dtype), self.jobs_dev.data_ptr(), self.n_jobs, self.rows_dev.data_ptr(),
+                                                 self.terms_dev.data_ptr(), self.max_cols, X._arena.data_ptr(), src2,
+                                                 res._arena.data_ptr(), dev.stream()), "mpo_expand")
+        return res
 
 
 def _envs_wide(LP, RP):

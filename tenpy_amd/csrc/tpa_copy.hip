@@ -5,6 +5,10 @@
 //                          (_npc_helper.pyx:1112-1123, :1235-1240 via _sliced_strided_copy :368) or one
 //                          per-block transpose of itranspose (:853).  The host builds the copy plan
 //                          from the integer bookkeeping; the device only moves bytes.
+//  * tpa_lincomb_batch / tpa_mpo_apply_batch / tpa_mpo_entry_apply_batch: the MPO step of the factored effective Hamiltonians
+//                          (block combinations, small matrices on the physical index, single entries); tpa_mpo_expand_batch: the
+//                          entry-by-entry step with a destination offset per row -- the expanded matrix of the subspace expansion
+//                          of single-site DMRG in one pass (reference mps_common.py:2140-2168, :2170-2199).
 //  * tpa_scale_axis_batch: iscale_axis (np_conserved.py:2132-2140).
 //  * tpa_gather_axis_batch: iproject's np.compress along one axis (np_conserved.py:1982).
 #include "tpa_common.h"
@@ -203,6 +207,28 @@ struct EntJob {   // int64[8]
 struct EntRow {   // int64[2]
     int64_t term_begin, term_count;
 };
+struct ExpRow {   // int64[4]: a row of tpa_mpo_expand_batch
+    int64_t term_begin, term_count, dst_row_off, src_sel;
+};
+
+// Where a row of a job lands and which source it reads: what tells the two entry points apart.  Everything else -- the walk over the
+// rows, the order of the terms, the multiply-adds -- is the one mpo_entry_job below.
+struct SlabRows {     // tpa_mpo_entry_apply_batch: row o of a job is o * post elements into the slab; one source
+    using Row = EntRow;
+    static __device__ __forceinline__ int64_t dst_ld(const EntJob &J) { return J.dst_ld ? J.dst_ld : J.n_rows * J.post; }
+    static __device__ __forceinline__ int64_t row_off(const Row &, int o, int64_t post) { return o * post; }
+    static __device__ __forceinline__ const double *source(const Row &, const double *src, const double *) { return src; }
+    static __device__ __forceinline__ bool row_even(const Row &) { return true; }
+};
+struct ScatteredRows {  // tpa_mpo_expand_batch: every row has a destination offset of its own and selects one of two sources
+    using Row = ExpRow;
+    static __device__ __forceinline__ int64_t dst_ld(const EntJob &J) { return J.dst_ld; }
+    static __device__ __forceinline__ int64_t row_off(const Row &r, int, int64_t) { return r.dst_row_off; }
+    static __device__ __forceinline__ const double *source(const Row &r, const double *src, const double *src2) {
+        return r.src_sel ? src2 : src;
+    }
+    static __device__ __forceinline__ bool row_even(const Row &r) { return (r.dst_row_off & 1) == 0; }
+};
 
 template <bool CPLX, bool VEC>
 __device__ __forceinline__ double2 ent_load(const double *x) {
@@ -223,23 +249,25 @@ __device__ __forceinline__ void ent_fma(double2 &acc, const LinTerm &t, const do
     }
 }
 
-template <bool CPLX, bool VEC>
-__device__ __forceinline__ void mpo_entry_job(const EntJob &J, const EntRow *__restrict__ R, const LinTerm *__restrict__ terms,
-                                              const double *__restrict__ src, double *__restrict__ dst) {
+template <bool CPLX, bool VEC, class P>
+__device__ __forceinline__ void mpo_entry_job(const EntJob &J, const typename P::Row *__restrict__ R, const LinTerm *__restrict__ terms,
+                                              const double *__restrict__ src, const double *__restrict__ src2,
+                                              double *__restrict__ dst) {
     constexpr int EPI = (!CPLX && VEC) ? 2 : 1;        // elements per item
     constexpr int CW = CPLX ? 2 : 1;                   // doubles per element
     const int n_rows = (int)J.n_rows;
     const int64_t post_items = J.post / EPI;
     const int64_t n_cols = J.pre * post_items;
-    const int64_t dst_ld = J.dst_ld ? J.dst_ld : J.n_rows * J.post;
+    const int64_t dst_ld = P::dst_ld(J);
     for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n_cols; e += (int64_t)gridDim.x * NT) {
         const int64_t i = e / post_items, j = (e - i * post_items) * EPI;
-        const double *x0 = src + CW * j;
         double *y = dst + CW * (J.dst_off + i * dst_ld + j);
-        EntRow r = R[0];
+        typename P::Row r = R[0];
         for (int o = 0; o < n_rows; ++o) {
             const LinTerm *T = terms + r.term_begin;
             const int nt = (int)r.term_count;
+            const double *x0 = P::source(r, src, src2) + CW * j;
+            double *yo = y + CW * P::row_off(r, o, J.post);
             if (o + 1 < n_rows) r = R[o + 1];          // the next row's entry is on its way while this row's terms are read
             double2 acc{0., 0.};
             int t = 0;
@@ -254,7 +282,6 @@ __device__ __forceinline__ void mpo_entry_job(const EntJob &J, const EntRow *__r
                 ent_fma<CPLX, VEC>(acc, T[t + 3], v3);
             }
             for (; t < nt; ++t) ent_fma<CPLX, VEC>(acc, T[t], ent_load<CPLX, VEC>(x0 + CW * (T[t].src_off + i * T[t].src_ld)));
-            double *yo = y + CW * o * J.post;
             if (VEC) {
                 *reinterpret_cast<double2 *>(yo) = acc;
             } else {
@@ -265,27 +292,49 @@ __device__ __forceinline__ void mpo_entry_job(const EntJob &J, const EntRow *__r
     }
 }
 
-template <bool CPLX, bool VEC>
-__global__ __launch_bounds__(NT) void mpo_entry_apply_kernel(const EntJob *__restrict__ jobs, const EntRow *__restrict__ rows,
-                                                             const LinTerm *__restrict__ terms, const double *__restrict__ src,
-                                                             double *__restrict__ dst) {
+// One job = blockIdx.y, for both row-addressing policies.
+template <bool CPLX, bool VEC, class P>
+__device__ __forceinline__ void mpo_entry_block(const EntJob *__restrict__ jobs, const typename P::Row *__restrict__ rows,
+                                                const LinTerm *__restrict__ terms, const double *__restrict__ src,
+                                                const double *__restrict__ src2, double *__restrict__ dst) {
     const EntJob J = jobs[blockIdx.y];
     if (J.pre <= 0 || J.n_rows <= 0 || J.post <= 0) return;
     if ((int64_t)blockIdx.x * NT >= J.pre * J.post) return;      // the grid is sized by the largest job: nothing left for this workgroup
-    const EntRow *R = rows + J.row_begin;
+    const typename P::Row *R = rows + J.row_begin;
     if (VEC && !CPLX) {         // two real elements per item: every address of the job has to stay on a 16-byte boundary
         bool even = ((J.post | J.dst_off | J.dst_ld) & 1) == 0;
         // every wavefront scans the tables of the job, lane l the rows l, l + 64, ...: the same answer in all of them
         for (int64_t o = threadIdx.x & 63; o < J.n_rows; o += 64) {
+            even = even && P::row_even(R[o]);
             const LinTerm *T = terms + R[o].term_begin;
             for (int64_t t = 0; t < R[o].term_count; ++t) even = even && ((T[t].src_off | T[t].src_ld) & 1) == 0;
         }
         if (!__all(even)) {
-            mpo_entry_job<CPLX, false>(J, R, terms, src, dst);
+            mpo_entry_job<CPLX, false, P>(J, R, terms, src, src2, dst);
             return;
         }
     }
-    mpo_entry_job<CPLX, VEC>(J, R, terms, src, dst);
+    mpo_entry_job<CPLX, VEC, P>(J, R, terms, src, src2, dst);
+}
+
+template <bool CPLX, bool VEC>
+__global__ __launch_bounds__(NT) void mpo_entry_apply_kernel(const EntJob *__restrict__ jobs, const EntRow *__restrict__ rows,
+                                                             const LinTerm *__restrict__ terms, const double *__restrict__ src,
+                                                             double *__restrict__ dst) {
+    mpo_entry_block<CPLX, VEC, SlabRows>(jobs, rows, terms, src, src, dst);
+}
+
+// ---- the fused matrix of the subspace expansion: mpo_entry_apply_kernel with a destination offset per row ---------------------------
+// What it replaces: LHeff / RHeff, iscale_axis, the tensordot over the fused leg and combine_legs of SubspaceExpansion (reference
+// mps_common.py:2140-2168, :2170-2199).  T1 = LP . theta (or theta . RP) is the source; a job is one cell (row slice x column slice) of
+// a charge block of the fused [(vL.p0), (wR.vR)] matrix, whose rows (p0', wR') lie one leading dimension apart for p0' and in other
+// column slices for wR' -- so every row carries its own offset from (dst_off + i dst_ld).  Rows of the stacked form read theta itself
+// (src2).  Launch geometry, summation and access widths are those of mpo_entry_apply_kernel above.
+template <bool CPLX, bool VEC>
+__global__ __launch_bounds__(NT) void mpo_expand_kernel(const EntJob *__restrict__ jobs, const ExpRow *__restrict__ rows,
+                                                        const LinTerm *__restrict__ terms, const double *__restrict__ src,
+                                                        const double *__restrict__ src2, double *__restrict__ dst) {
+    mpo_entry_block<CPLX, VEC, ScatteredRows>(jobs, rows, terms, src, src2, dst);
 }
 
 struct ScaleJob {  // int64[6]
@@ -502,6 +551,38 @@ extern "C" int tpa_mpo_entry_apply_batch(int dtype, const int64_t *jobs_dev, int
             mpo_entry_apply_kernel<true, true><<<grid, NT, 0, st>>>(jobs, rows, terms, src, dst);
         else
             mpo_entry_apply_kernel<true, false><<<grid, NT, 0, st>>>(jobs, rows, terms, src, dst);
+    }
+    TPA_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int tpa_mpo_expand_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const int64_t *rows_dev, const int64_t *terms_dev,
+                                    int64_t max_job_cols, const void *src_base, const void *src2_base, void *dst_base, void *stream) {
+    TPA_ARG_CHECK(dtype == TPA_F64 || dtype == TPA_C128);
+    if (n_jobs <= 0) return 0;
+    TPA_ARG_CHECK(n_jobs <= 65535);
+    const bool aligned = (((uintptr_t)src_base | (uintptr_t)src2_base | (uintptr_t)dst_base) & 15) == 0;
+    const int64_t items = (dtype == TPA_F64 && aligned) ? (max_job_cols + 1) / 2 : max_job_cols;
+    int64_t g = (items + NT - 1) / NT;
+    if (g < 1) g = 1;
+    if (g > 512) g = 512;
+    dim3 grid((int)g, n_jobs);
+    hipStream_t st = (hipStream_t)stream;
+    const EntJob *jobs = (const EntJob *)jobs_dev;
+    const ExpRow *rows = (const ExpRow *)rows_dev;
+    const LinTerm *terms = (const LinTerm *)terms_dev;
+    const double *src = (const double *)src_base, *src2 = (const double *)src2_base;
+    double *dst = (double *)dst_base;
+    if (dtype == TPA_F64) {
+        if (aligned)
+            mpo_expand_kernel<false, true><<<grid, NT, 0, st>>>(jobs, rows, terms, src, src2, dst);
+        else
+            mpo_expand_kernel<false, false><<<grid, NT, 0, st>>>(jobs, rows, terms, src, src2, dst);
+    } else {
+        if (aligned)
+            mpo_expand_kernel<true, true><<<grid, NT, 0, st>>>(jobs, rows, terms, src, src2, dst);
+        else
+            mpo_expand_kernel<true, false><<<grid, NT, 0, st>>>(jobs, rows, terms, src, src2, dst);
     }
     TPA_LAUNCH_CHECK();
     return 0;

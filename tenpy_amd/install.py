@@ -19,7 +19,7 @@ a TeNPy that keeps its own ``np_conserved`` -- is ``tenpy_amd/_npc_helper.py``.
 fused form: ``LanczosGroundState`` (one fused recurrence kernel per step instead of four BLAS-1 calls), ``TwoSiteH``
 (cached plans; factored matvec LP . theta . W0 W1 . RP for ``combine=False``), the bond hint of the warm-started block
 SVD, ``OrthogonalNpcLinearOperator`` (the projections of an excited-state search inside the native Krylov loop), and for TDVP ``LanczosEvolution`` (one native loop and one combination pass per evolution) with the device ``OneSiteH`` /
-``ZeroSiteH``, and ``SumNpcLinearOperator`` (``H + h.c.`` of an MPO with ``explicit_plus_hc`` as one device operator); see
+``ZeroSiteH``, the subspace expansion of ``SingleSiteDMRGEngine`` (one ``tpa_mpo_expand_batch`` launch with a device ``OneSiteH``), and ``SumNpcLinearOperator`` (``H + h.c.`` of an MPO with ``explicit_plus_hc`` as one device operator); see
 :func:`use_fused_callers`.
 """
 import importlib
@@ -105,6 +105,11 @@ def use_fused_callers():
     * ``TwoSiteDMRGEngine.mixed_svd`` (``dmrg.py:876``) is wrapped to pass the bond index to the block SVD (warm start).
     * ``DensityMatrixMixer.mix_rho`` (``mps_common.py:1972``) is wrapped in place: with a device ``TwoSiteH`` the density matrices are
       one ``tpa_herk_chain`` launch per side (``algorithms/mixer.py``), else the reference's statements.
+    * ``SubspaceExpansion.mix_and_decompose_1site`` (``mps_common.py:2133``) is wrapped in place, and ``OneSiteH`` as ``dmrg`` knows it
+      and ``SingleSiteDMRGEngine.EffectiveH`` (``dmrg.py:974``) are a device ``OneSiteH`` that also takes the chain's boundary environments: with it the expanded matrix of single-site
+      DMRG is one GEMM over chi and one ``tpa_mpo_expand_batch`` launch (``mixer.device_expand_1site``; ``LHeff`` / ``RHeff`` are not
+      built), else -- ``combine=True``, ``explicit_plus_hc``, infinite systems, sites the device class hands back -- the reference's
+      method runs (``module_form.stats['expand_device']`` / ``['expand_reference']``).
     * ``TEBDEngine.evolve_step`` (``tebd.py:374``; inherited by ``QRBasedTEBDEngine``) -> the bonds of a half-step decomposed in one
       batched device call (``module_form.batched_tebd_evolve_step``; the per-bond statements stay the reference's).
     * ``LanczosEvolution`` (``linalg/krylov_based.py:718``; constructed at ``tdvp.py:132 _krylov_evolve``) -> the device class: the
@@ -112,8 +117,8 @@ def use_fused_callers():
       offers a launch program; ``OneSiteH`` / ``ZeroSiteH`` (``mps_common.py:1040`` / ``:1440``; ``tdvp.py:308`` / ``:419``) -> the
       device forms of ``module_form`` (factored matvec with cached plans), which hand what they do not cover back to the
       reference's classes; ``TwoSiteTDVPEngine.EffectiveH`` / ``SingleSiteTDVPEngine.EffectiveH`` (``tdvp.py:248`` / ``:333``) get the
-      device ``TwoSiteH`` / ``OneSiteH``, so that the forward evolutions run natively too.  ``OneSiteH`` / ``ZeroSiteH`` are rebound in
-      ``mps_common`` and ``tdvp`` only: DMRG, VUMPS and the plane-wave excitations keep theirs.
+      device ``TwoSiteH`` / ``OneSiteH``, so that the forward evolutions run natively too.  ``OneSiteH`` is rebound in ``mps_common``,
+      ``tdvp`` and ``dmrg``, ``ZeroSiteH`` in ``mps_common`` and ``tdvp`` only: VUMPS and the plane-wave excitations keep theirs.
     * ``OrthogonalNpcLinearOperator`` (``linalg/sparse.py:220``; constructed at ``mps_common.py:540 _wrap_ortho_eff_H``, where it is
       imported by name) -> the device class of ``tenpy_amd/linalg/sparse.py`` (same constructor, same ``gram_schmidt``, same
       ``matvec``), whose ``native_input`` puts the two projections into the launch program of the operator it wraps: the engines'
@@ -143,6 +148,9 @@ def use_fused_callers():
         ref_dmrg.TwoSiteDMRGEngine.mixed_svd = module_form.hinted_mixed_svd(ref_dmrg.TwoSiteDMRGEngine.mixed_svd)
     if not getattr(ref_mc.DensityMatrixMixer.mix_rho, '_tpa_wrapped', False):
         ref_mc.DensityMatrixMixer.mix_rho = module_form.device_mixer_mix_rho(ref_mc.DensityMatrixMixer.mix_rho)
+    if not getattr(ref_mc.SubspaceExpansion.mix_and_decompose_1site, '_tpa_wrapped', False):
+        ref_mc.SubspaceExpansion.mix_and_decompose_1site = module_form.device_subspace_expansion(
+            ref_mc.SubspaceExpansion.mix_and_decompose_1site, ref_mc)
     import tenpy.algorithms.tebd as ref_tebd
     if not getattr(ref_tebd.TEBDEngine.evolve_step, '_tpa_wrapped', False):
         ref_tebd.TEBDEngine.evolve_step = module_form.batched_tebd_evolve_step(ref_tebd)
@@ -151,6 +159,9 @@ def use_fused_callers():
     ref_tdvp.LanczosEvolution = kb.LanczosEvolution
     if not hasattr(ref_mc.OneSiteH, '_reference_class'):
         ref_mc.OneSiteH = ref_tdvp.OneSiteH = module_form.device_one_site_h(ref_mc.OneSiteH)
+    if not getattr(ref_dmrg.OneSiteH, '_boundary_envs', False):      # (a class of its own: it also takes the boundary environments)
+        ref_dmrg.OneSiteH = ref_dmrg.SingleSiteDMRGEngine.EffectiveH = module_form.device_one_site_h(
+            getattr(ref_mc.OneSiteH, '_reference_class', ref_mc.OneSiteH), boundary_envs=True)
     # `import tenpy` has imported tdvp already: the names and class attributes bound there are re-pointed one by one
     ref_tdvp.TwoSiteH = ref_tdvp.TwoSiteTDVPEngine.EffectiveH = ref_mc.TwoSiteH
     ref_tdvp.SingleSiteTDVPEngine.EffectiveH = ref_mc.OneSiteH

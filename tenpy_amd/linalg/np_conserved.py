@@ -1653,6 +1653,7 @@ def clear_device_caches():
         _mc.MpoApplyPlan._cache.clear()
         _mc.MpoBlockApplyPlan._cache.clear()
         _mc.MpoEntryApplyPlan._cache.clear()
+        _mc.MpoExpandPlan._cache.clear()
         _mc._skip_table_cache.clear()
     except ImportError:      # (the linalg package is importable on its own)
         pass
