@@ -329,6 +329,35 @@ int tpa_mpo_entry_apply_batch(int dtype, const int64_t *jobs_dev, int n_jobs, co
  * job); 8-byte ones otherwise. */
 int tpa_mpo_expand_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const int64_t *rows_dev, const int64_t *terms_dev,
                          int64_t max_job_cols, const void *src_base, const void *src2_base, void *dst_base, void *stream);
+/* A cell of a fused [(vL.p), (wR.vR)] matrix as one small dense product: the rows of a job = coeff (n_rows x n_src) times the job's
+ * DISTINCT source rows.  It serves the zip-up application of an MPO to an MPS (reference mpo.py:1733-1757: tensordot(B, W),
+ * combine_legs) for MPO tensors that are dense in the bond index (U_I / U_II), where the N rows of a cell draw on the same K source
+ * rows: tpa_mpo_expand_batch loads N K source items per column item of the cell, this entry point K (and stores N).
+ * jobs : int64[n_jobs][10] = {dst_off, pre, n_rows, post, dst_ld, row_begin, src_begin, n_src, coeff_off, 0}
+ * rows : int64[..][2]      = {dst_row_off, 0}                  row o of a job: rows[row_begin + o]
+ * srcs : int64[..][2]      = {src_off, src_ld}                 source k of a job: srcs[src_begin + k]
+ * coeff: elements of dtype; coefficient of (row o, source k) of a job at coeff[coeff_off + k*n_rows + o]
+ *   dst[dst_off + i*dst_ld + dst_row_off_o + j] = sum_{k < n_src} coeff(o,k) * src[src_off_k + i*src_ld_k + j]
+ *   for i < pre, o < n_rows, j < post
+ * Offsets and strides in elements of dtype.  1 <= max_rows <= TPA_MPO_CELL_MAXROWS and max_rows >= n_rows of every job (it selects the
+ * number of accumulators a thread keeps: 8, 16 or 32); rows o >= max_rows of a job that breaks this are not written (the max_d
+ * convention of tpa_mpo_apply_batch).  Several jobs may share one source list and differ in coeff_off (a cell with more than
+ * TPA_MPO_CELL_MAXROWS rows is split that way).  max_job_cols = max pre * post over the jobs sizes the grid, capped at 512 workgroups
+ * per job (larger jobs loop).  One job per blockIdx.y like the other batched entry points of this section: dtype, then max_rows are
+ * checked first, then n_jobs <= 0 returns 0 without a launch and n_jobs > 65535 returns TPA_E_BADARG; all argument errors before
+ * anything is launched; jobs with a zero extent do nothing.  Exactly the listed elements are written, each once -- the caller
+ * guarantees that the rows of a launch do not overlap; a job with n_src = 0 writes zeros --, nothing else is written; src and dst must
+ * not overlap.  Summation order: k ascending, one chain of fused multiply-adds per component, zero coefficients included, the complex
+ * pattern of tpa_mpo_expand_batch -- on finite data the result compares equal (==) to tpa_mpo_expand_batch fed the nonzero
+ * coefficients in the same order, and two identical calls give identical bits.  A thread owns one column item (i, j) of its job,
+ * loads every source item once and updates the accumulators of all rows; the coefficients go through uniform (scalar) loads.
+ * Traffic: itemsize (sum_jobs pre post (n_src + n_rows)) bytes.  16-byte loads and stores where src_base and dst_base are 16-byte
+ * aligned and, for F64, post, dst_off, dst_ld and every dst_row_off, src_off and src_ld of the job are even (decided per job); 8-byte
+ * ones otherwise. */
+#define TPA_MPO_CELL_MAXROWS 32
+int tpa_mpo_cell_apply_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const int64_t *rows_dev, const int64_t *srcs_dev,
+                             const void *coeff_dev, int max_rows, int64_t max_job_cols, const void *src_base, void *dst_base,
+                             void *stream);
 /* x_b[i, j, l] *= s[s_off_b + j]  for each block b viewed as (pre, len, post).  Replaces
  * iscale_axis, np_conserved.py:2132-2140.  jobs: int64[n][6] = {x_off, pre, len, post, s_off, 0};
  * the scale vector s is real (F64) or of `dtype` when s_is_complex. */

@@ -17,6 +17,7 @@ E_BADARG, E_NOCONV, E_NAN, E_NOMEM, E_RANKCAP = -1, -2, -3, -4, -5
 PROJECT_MAX = 64                              # TPA_PROJECT_MAX
 PROJECT_WORK = 2 * 1024 * (PROJECT_MAX + 1)   # TPA_PROJECT_WORK (doubles)
 MPO_APPLY_MAXD = 16                           # TPA_MPO_APPLY_MAXD
+MPO_CELL_MAXROWS = 32                         # TPA_MPO_CELL_MAXROWS
 
 _lib = None
 
@@ -57,6 +58,7 @@ _SIGS = {
     "tpa_mpo_apply_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp]),
     "tpa_mpo_entry_apply_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp]),
     "tpa_mpo_expand_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "tpa_mpo_cell_apply_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp]),
     "tpa_svd_dyn_stats": (ctypes.c_int, [_i64p, ctypes.c_int]),
     "tpa_tri_lower_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int64, _vp, _vp]),
     "tpa_scale_axis_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, ctypes.c_int, _vp]),

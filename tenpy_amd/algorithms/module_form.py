@@ -56,7 +56,12 @@ stats = {'device': 0, 'reference': 0,      # bonds handled by the device form / 
          'mixer_device': 0, 'mixer_reference': 0,
          # SubspaceExpansion.mix_and_decompose_1site: expansions served by `mixer.device_expand_1site` (one tpa_mpo_expand_batch launch) / by
          # the reference's method
-         'expand_device': 0, 'expand_reference': 0}
+         'expand_device': 0, 'expand_reference': 0,
+         # MPO.apply_zipup: sites whose matrix came from `mps_common.device_zipup_step` / from the reference's statements (of these:
+         # the two boundary sites of every pass); whole passes handed to the reference's method with ONE counted decline
+         # (`explicit_plus_hc`, not finite: it refuses them before its loop); declines by reason: `mps_common.zipup_stats['why']`, so
+         # zipup_reference - zipup_boundary == declined - zipup_handed_back
+         'zipup_device': 0, 'zipup_reference': 0, 'zipup_boundary': 0, 'zipup_handed_back': 0}
 
 
 def device_two_site_h(Ref):
@@ -314,6 +319,64 @@ def device_subspace_expansion(ref_method, ref_mc):
     mix_and_decompose_1site.__doc__ = ref_method.__doc__
     mix_and_decompose_1site._tpa_wrapped = True
     return mix_and_decompose_1site
+
+
+def device_apply_zipup(ref_method, ref_mpo):
+    """Wraps ``MPO.apply_zipup`` (networks/mpo.py:1679-1767) IN PLACE, like ``device_subspace_expansion``: the statements of the reference's
+    pass with the matrix of every interior site taken from ``mps_common.device_zipup_step`` -- one GEMM over chi and the MPO step on the
+    device; ``tensordot(B, W)``, an intermediate of chi^2 D^2 d elements, is not built.  The two boundary sites, and interior sites the
+    device route declines (counted with the reason), run the reference's own statements; what the reference refuses before its loop
+    (boundary conditions, lengths, ``explicit_plus_hc``) is handed to its method."""
+    def apply_zipup(self, psi, options):
+        finite = psi.bc == 'finite' and self.bc == 'finite'
+        if self.explicit_plus_hc or not finite:      # one decline, counted with its reason, for the whole pass
+            declined = dev_mc.device_zipup_step(None, None, None, explicit_plus_hc=self.explicit_plus_hc, finite=finite)
+            assert declined is None
+            stats['zipup_handed_back'] += 1
+            return ref_method(self, psi, options)
+        if psi.L != self.L or psi.L < 3:
+            return ref_method(self, psi, options)
+        svd_theta, ref_npc = ref_mpo.svd_theta, ref_mpo.npc
+        options = ref_mpo.asConfig(options, 'zip_up')
+        m_temp = options.get('m_temp', 2, int)
+        trunc_weight = options.get('trunc_weight', 1., 'real')
+        trunc_params = options.subconfig('trunc_params')
+        relax_trunc = trunc_params.copy()
+        relax_trunc['chi_max'] *= m_temp
+        if 'svd_min' in relax_trunc.keys():
+            relax_trunc['svd_min'] *= trunc_weight
+        trunc_err = ref_mpo.TruncationError()
+        VH = None
+        for i in range(psi.L):
+            last = i == psi.L - 1
+            B = dev_mc.device_zipup_step(VH, psi.get_B(i, 'B'), self.get_W(i)) if 0 < i and not last else None
+            if B is not None:
+                stats['zipup_device'] += 1
+            else:
+                stats['zipup_reference'] += 1
+                stats['zipup_boundary'] += i == 0 or last
+                B = ref_npc.tensordot(psi.get_B(i, 'B'), self.get_W(i), axes=('p', 'p*'))
+                if i == 0:
+                    B = B.take_slice(self.get_IdL(i), 'wL')
+                else:
+                    B = ref_npc.tensordot(VH, B, axes=(['wR', 'vR'], ['wL', 'vL']))
+                if last:
+                    B = B.take_slice(self.get_IdR(i), 'wR').combine_legs(['vL', 'p'], qconj=[-1])
+                else:
+                    B = B.combine_legs([['vL', 'p'], ['wR', 'vR']], qconj=[+1, -1])
+            U, S, VH, err, norm_new = svd_theta(B, relax_trunc, [B.qtotal, None]) if last else svd_theta(B, relax_trunc)
+            trunc_err += err
+            psi.norm *= norm_new
+            U = U.split_legs()
+            if not last:
+                VH = VH.split_legs()
+                VH.iscale_axis(S, 'vL')
+            psi.set_SR(i, S)
+            psi.set_B(i, U, 'A')
+        return trunc_err
+    apply_zipup.__doc__ = ref_method.__doc__
+    apply_zipup._tpa_wrapped = True
+    return apply_zipup
 
 
 def batched_tebd_evolve_step(ref_tebd):

@@ -735,6 +735,8 @@ class MpoExpandPlan(_MpoStepPlan):
     _cache = {}
     _table = staticmethod(_mpo_coo)
     MAX_JOBS = 60000        # (the entry point takes 65535; the margin of the sibling plans)
+    _P = ('p0', 'p0*')      # labels of the physical legs of W: the open one and the one contracted with T1
+    _X_RIGHT = ['vR*', 'wR', 'p0', 'vR']        # labels of T1 moving right
 
     @classmethod
     def get(cls, X, W, move_right, zero, proj=None, theta=None, row_pipe=None):
@@ -756,11 +758,12 @@ class MpoExpandPlan(_MpoStepPlan):
     def __init__(self, X, W, move_right, zero, proj=None, theta=None, row_pipe=None):
         from ..linalg.charges import LegCharge, LegPipe
         w_in, w_out = ('wL', 'wR') if move_right else ('wR', 'wL')
-        want = ['vR*', 'wR', 'p0', 'vR'] if move_right else ['vL', 'p0', 'wL', 'vL*']
-        assert list(X.get_leg_labels()) == want and list(W.get_leg_labels()) == ['wL', 'wR', 'p0', 'p0*']
+        p_out, p_in = self._P
+        want = self._X_RIGHT if move_right else ['vL', 'p0', 'wL', 'vL*']
+        assert list(X.get_leg_labels()) == want and list(W.get_leg_labels()) == ['wL', 'wR', p_out, p_in]
         ax_w, ax_p = (1, 2) if move_right else (2, 1)
-        keys, vals = MpoEntryApplyPlan._entries(W, w_in, w_out, 'p0', 'p0*')      # (w_in, w_out, p_out, p_in)
-        wleg, pleg = W.get_leg(w_out), W.get_leg('p0')
+        keys, vals = MpoEntryApplyPlan._entries(W, w_in, w_out, p_out, p_in)      # (w_in, w_out, p_out, p_in)
+        wleg, pleg = W.get_leg(w_out), W.get_leg(p_out)
         zero = np.asarray(zero, bool)
         assert zero.shape == (wleg.ind_len,)
         w_new = keys[:, 1]
@@ -782,7 +785,7 @@ class MpoExpandPlan(_MpoStepPlan):
         if move_right:
             self.row_pipe = row_pipe if row_pipe is not None else LegPipe([X.legs[0], pleg], qconj=+1)
             self.col_pipe = LegPipe([wleg, X.legs[3]], qconj=-1)
-            self.labels = ['(vL.p0)', '(wR.vR)']
+            self.labels = ['(vL.%s)' % p_out, '(wR.vR)']
         else:
             self.row_pipe = LegPipe([X.legs[0], wleg], qconj=+1)
             self.col_pipe = row_pipe if row_pipe is not None else LegPipe([pleg, X.legs[3]], qconj=-1)     # (the given pipe of theta)
@@ -803,14 +806,14 @@ class MpoExpandPlan(_MpoStepPlan):
         pr = dict(v0=xq[ib, 0], v1=xq[ib, 3], bw=bw[ie], pw=pw[ie], bp=bp[ie], pp=pp[ie],
                   off=X._offsets[ib] + (pos_in[1][ie] * shapes_x[ib, 2] + pos_in[2][ie]) * post_x,
                   ld=shapes_x[ib, 1] * shapes_x[ib, 2] * post_x, val=vals[ie].astype(np.complex128), w=keys[ie, 1],
-                  sel=np.zeros(len(ib), np.int64))
+                  sel=np.zeros(len(ib), np.int64), blk=ib)
         if self.stacked and theta.stored_blocks:       # the rows of theta: one term each, alpha = 1, read from the second source
             tq, ts = theta._qdata, theta._block_shapes()
             tb = np.repeat(np.arange(len(tq)), ts[:, 1])
             tp = np.arange(len(tb)) - np.repeat(np.cumsum(ts[:, 1]) - ts[:, 1], ts[:, 1])
             z = np.zeros(len(tb), np.int64)
             th = dict(v0=tq[tb, 0], v1=tq[tb, 2], bw=z, pw=z, bp=tq[tb, 1], pp=tp, off=theta._offsets[tb] + tp * ts[tb, 2],
-                      ld=ts[tb, 1] * ts[tb, 2], val=np.ones(len(tb), np.complex128), w=z - 1, sel=z + 1)
+                      ld=ts[tb, 1] * ts[tb, 2], val=np.ones(len(tb), np.complex128), w=z - 1, sel=z + 1, blk=tb)
             pr = {k: np.concatenate([pr[k], th[k]]) for k in pr}
             self.theta_key = theta._struct_key()
         self.empty = len(pr['off']) == 0
@@ -872,6 +875,7 @@ class MpoExpandPlan(_MpoStepPlan):
         terms = np.zeros((max(len(key), 1), 4), dtype=np.int64)
         terms[:len(key), 0], terms[:len(key), 1] = pr['off'][key], pr['ld'][key]
         self.term_val, self.term_w = pr['val'][key], pr['w'][key]
+        self.term_blk, self.term_row = pr['blk'][key], row[key]       # (block of the source and row of every term: the cell-dense form)
         if self.dtype.kind != 'c':
             assert np.all(self.term_val.imag == 0)
         self.jobs_host, self.rows_host, self.terms_host, self.sizes = jobs, rows, terms, sizes
@@ -908,6 +912,225 @@ class MpoExpandPlan(_MpoStepPlan):
                                                  self.terms_dev.data_ptr(), self.max_cols, X._arena.data_ptr(), src2,
                                                  res._arena.data_ptr(), dev.stream()), "mpo_expand")
         return res
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Zip-up application of an MPO to an MPS (reference ``MPO.apply_zipup``, mpo.py:1679-1767).  At an interior site the reference decomposes
+#     M[(vL.p), (wR.vR)] = sum_{w, p*} W[w, wR, p, p*] T1[vL, w, p*, vR],      T1 = VH_prev[vL, w, vR'] . B[vR', p*, vR]
+# and gets it as tensordot(B, W) -- an intermediate of chi^2 D^2 d elements --, a tensordot over (w, vR') and ``combine_legs``.  It is the
+# matrix of ``MpoExpandPlan`` moving right with ``VH_prev`` in the place of ``LP`` and all weights 1: one GEMM over chi and the MPO step.
+# Time-evolution MPOs (U_I, U_II) are dense in the bond index: the rows of a cell share their source rows, and the cell-dense form
+# (``tpa_mpo_cell_apply_batch``) loads each of them once.
+from .._lib import MPO_CELL_MAXROWS    # noqa: E402  (TPA_MPO_CELL_MAXROWS)
+# Which cells of a zip-up step take the cell-dense launch: 0 = none (the entry-by-entry launch of the subspace expansion alone), 1 = the
+# cells ``MpoZipupPlan._cell_rule`` selects, 2 = every cell with a source.  The default follows profiles/mpo_zipup.txt: the forced
+# cell-dense route is slower than the entry launch on the 4-wide nearest-neighbour structure, so it is 0.
+MPO_CELL_DEFAULT = '0'
+
+
+def mpo_cell_mode():
+    return int(_os.environ.get('TPA_MPO_CELL', MPO_CELL_DEFAULT))
+
+
+zipup_stats = {'device_steps': 0, 'declined': 0, 'why': {}, 'plans_built': 0, 'cell_launches': 0, 'entry_launches': 0}
+
+
+def reset_zipup_stats():
+    zipup_stats.update(device_steps=0, declined=0, why={}, plans_built=0, cell_launches=0, entry_launches=0)
+
+
+class _ZipupRoute:
+    """The launches of one ``MpoZipupPlan`` under one setting of ``TPA_MPO_CELL``: the jobs of the cell-dense launch and the jobs left to
+    the entry-by-entry launch (disjoint destinations)."""
+
+    def __init__(self, plan, cell):
+        piece_cell = cell[plan.piece_job]
+        cj, ej = plan.cell_jobs_host[piece_cell], plan.jobs_host[~cell]
+        if len(cj) > plan.MAX_JOBS:
+            raise ExpandJobLimit("%d jobs for one tpa_mpo_cell_apply_batch launch" % len(cj))
+        if len(ej) > plan.MAX_JOBS:
+            raise ExpandJobLimit("%d jobs for one tpa_mpo_expand_batch launch" % len(ej))
+        self.n_cell, self.n_entry = len(cj), len(ej)
+        self.cell_jobs_dev = dev.to_device(cj) if len(cj) else None
+        self.entry_jobs_dev = (plan.jobs_dev if len(ej) == len(plan.jobs_host) else dev.to_device(ej)) if len(ej) else None
+        self.max_rows = int(np.max(cj[:, 2])) if len(cj) else 0
+        self.cell_cols = int(np.max(cj[:, 1] * cj[:, 3])) if len(cj) else 0
+        self.entry_cols = int(np.max(ej[:, 1] * ej[:, 3])) if len(ej) else 0
+
+
+class MpoZipupPlan(MpoExpandPlan):
+    """``MpoExpandPlan`` moving right for the zip-up step -- ``X = T1 [vL, wR, p, vR]``, ``W [wL, wR, p, p*]``, all weights 1, result
+    ``[(vL.p), (wR.vR)]`` with the pipes of the reference's ``combine_legs`` -- with a CELL-DENSE table form next to the entry tables:
+    per cell the distinct source rows (ordered by block of T1 and position inside it: the order in which every row of the entry tables
+    lists them, ``ordered``) and the ``n_rows x n_src`` coefficient matrix, zero where W has no entry, for
+    ``tpa_mpo_cell_apply_batch``.  Cells with more than ``TPA_MPO_CELL_MAXROWS`` rows are split into jobs over the same source list.
+    ``apply`` sends every cell to one of at most two launches (``TPA_MPO_CELL``); both sum the same chain of fused multiply-adds, so the
+    choice does not change a bit of the result (a plan that is not ``ordered`` keeps to the entry launch)."""
+    _cache = {}
+    MAX_JOBS = 60000
+    _P = ('p', 'p*')
+    _X_RIGHT = ['vL', 'wR', 'p', 'vR']
+
+    @classmethod
+    def get(cls, X, W, row_pipe=None):
+        return super().get(X, W, True, np.zeros(W.get_leg('wR').ind_len, bool), None, None, row_pipe)
+
+    def __init__(self, X, W, move_right, zero, proj=None, theta=None, row_pipe=None):
+        assert move_right and proj is None and not np.any(zero)
+        super().__init__(X, W, True, zero, None, None, row_pipe)
+        self._routes = {}
+        if self.empty:
+            return
+        jobs, nt = self.jobs_host, len(self.term_val)
+        n_rows, row_begin = jobs[:, 2], jobs[:, 4]
+        t_row = self.term_row
+        t_job = np.repeat(np.arange(len(jobs)), n_rows)[t_row]
+        # the distinct sources of every cell, by (block of T1, offset)
+        uq, inv = np.unique(np.stack([t_job, self.term_blk, self.terms_host[:nt, 0]], axis=1), axis=0, return_inverse=True)
+        inv = inv.reshape(-1)
+        n_src = np.bincount(uq[:, 0], minlength=len(jobs)).astype(np.int64)
+        src_begin = np.cumsum(n_src) - n_src
+        k = inv - src_begin[t_job]
+        srcs = np.zeros((max(len(uq), 1), 2), dtype=np.int64)
+        srcs[:len(uq), 0] = uq[:, 2]
+        srcs[inv, 1] = self.terms_host[:nt, 1]
+        same = t_row[1:] == t_row[:-1]
+        self.ordered = bool(np.all(k[1:][same] > k[:-1][same]))      # every row lists its sources in the order of the cell
+        # jobs of at most MPO_CELL_MAXROWS rows
+        n_piece = -(-n_rows // MPO_CELL_MAXROWS)
+        pj = np.repeat(np.arange(len(jobs)), n_piece)
+        piece_begin = np.cumsum(n_piece) - n_piece
+        r0 = (np.arange(len(pj)) - piece_begin[pj]) * MPO_CELL_MAXROWS
+        p_rows = np.minimum(MPO_CELL_MAXROWS, n_rows[pj] - r0)
+        c_size = p_rows * n_src[pj]
+        c_off = np.cumsum(c_size) - c_size
+        cj = np.zeros((len(pj), 10), dtype=np.int64)
+        cj[:, 0], cj[:, 1], cj[:, 2], cj[:, 3], cj[:, 4] = jobs[pj, 0], jobs[pj, 1], p_rows, jobs[pj, 3], jobs[pj, 5]
+        cj[:, 5], cj[:, 6], cj[:, 7], cj[:, 8] = row_begin[pj] + r0, src_begin[pj], n_src[pj], c_off
+        o = t_row - row_begin[t_job]
+        piece = piece_begin[t_job] + o // MPO_CELL_MAXROWS
+        coeff = np.zeros(max(int(np.sum(c_size)), 1), dtype=self.dtype)
+        val = self.term_val if self.dtype.kind == 'c' else self.term_val.real
+        at = c_off[piece] + k * p_rows[piece] + o % MPO_CELL_MAXROWS
+        assert len(np.unique(at)) == len(at), "a row lists one source twice"      # (an entry of W per (row, source): nothing to add up)
+        coeff[at] = val
+        self.cell_jobs_host, self.piece_job, self.srcs_host, self.coeff_host = cj, pj, srcs, coeff
+        self.cell_n_src, self.cell_nnz = n_src, np.bincount(t_job, minlength=len(jobs)).astype(np.int64)
+        self.cell_rows_dev = dev.to_device(np.ascontiguousarray(np.stack([self.rows_host[:, 2], np.zeros(len(self.rows_host), np.int64)], axis=1)))
+        self.srcs_dev, self.coeff_dev = dev.to_device(srcs), dev.to_device(coeff)
+        cols = jobs[:, 1] * jobs[:, 3]
+        item = 8 * (2 if self.dtype.kind == 'c' else 1)
+        self.cell_bytes = item * int(np.sum(cols * (n_src + n_rows)))      # every cell by the cell-dense launch
+
+    @staticmethod
+    def _cell_rule(n_src, n_rows, nnz):
+        """The cells that the cell-dense launch takes under ``TPA_MPO_CELL=1``: the entry tables load ``nnz`` source rows per column
+        item of the cell, the cell-dense form ``n_src`` -- it takes the cells where that halves the loads at least AND that have 6
+        rows or more.  Measured (profiles/mpo_zipup.txt, chi = 1024, complex and real): cells of 6 and 12 rows over 9 and 18 sources
+        run 2.2 to 2.6 times faster in the cell-dense form, cells of 12 and 24 rows over 18 and 36 sources (one launch on the
+        32-accumulator kernel: the largest job of a launch selects it for all of them) 2.1 to 3 times; cells of 1 and 2 rows over at
+        most 3 sources are served from the caches either way and the entry form is up to 10 % faster there.  Not measured: cells of 3
+        to 5 rows (they stay where they were), and a launch that mixes a few cells above 16 rows with many small ones, which all run
+        with 32 accumulators then."""
+        return (n_src >= 1) & (n_rows >= 6) & (nnz >= 2 * n_src)
+
+    def route(self, mode):
+        r = self._routes.get(mode)
+        if r is None:
+            if mode == 0 or not self.ordered:      # (out of order the two launches would sum differently: the entry launch alone)
+                cell = np.zeros(len(self.jobs_host), bool)
+            elif mode == 2:
+                cell = self.cell_n_src >= 1
+            else:
+                cell = self._cell_rule(self.cell_n_src, self.jobs_host[:, 2], self.cell_nnz)
+            r = self._routes[mode] = _ZipupRoute(self, cell)
+        return r
+
+    def apply(self, X, mode=None):
+        """M as a new Array: at most one cell-dense and one entry-by-entry launch (``mode``: ``TPA_MPO_CELL``)."""
+        res = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
+        if self.empty:
+            return res
+        assert X._struct_key() == self.x_key and X.dtype == self.dtype
+        r = self.route(mpo_cell_mode() if mode is None else mode)
+        res._set_blocks(self.qdata, arena=dev.empty(self.total, self.dtype), qdata_sorted=True)
+        code, L = dev.code(self.dtype), dev.lib()
+        if r.n_entry:
+            self._set_weights(np.ones(self.w_leg.ind_len))
+            dev.check(L.tpa_mpo_expand_batch(code, r.entry_jobs_dev.data_ptr(), r.n_entry, self.rows_dev.data_ptr(),
+                                             self.terms_dev.data_ptr(), r.entry_cols, X._arena.data_ptr(), None,
+                                             res._arena.data_ptr(), dev.stream()), "mpo_expand")
+            zipup_stats['entry_launches'] += 1
+        if r.n_cell:
+            dev.check(L.tpa_mpo_cell_apply_batch(code, r.cell_jobs_dev.data_ptr(), r.n_cell, self.cell_rows_dev.data_ptr(),
+                                                 self.srcs_dev.data_ptr(), self.coeff_dev.data_ptr(), r.max_rows, r.cell_cols,
+                                                 X._arena.data_ptr(), res._arena.data_ptr(), dev.stream()), "mpo_cell")
+            zipup_stats['cell_launches'] += 1
+        return res
+
+
+def zipup_enabled():
+    return _os.environ.get('TPA_ZIPUP_DEVICE', '1') != '0'
+
+
+def _zipup_declines(VH_prev, B, W, explicit_plus_hc, finite):
+    """Why the device route of the zip-up step does not take this call (counted in ``zipup_stats['why']``), or ``None``."""
+    if not zipup_enabled():
+        return 'switched off'
+    if explicit_plus_hc:
+        return 'explicit_plus_hc'
+    if not finite:
+        return 'not finite'
+    if not (dev.lib_provides('tpa_mpo_expand_batch') and dev.lib_provides('tpa_mpo_cell_apply_batch')):
+        return 'entry point'      # an emulation that predates the entry points: never forwarded to the real library
+    if VH_prev.stored_blocks == 0 or B.stored_blocks == 0 or W.stored_blocks == 0:
+        return 'empty tensor'
+    return None
+
+
+def _zipup_decline(why):
+    zipup_stats['declined'] += 1
+    zipup_stats['why'][why] = zipup_stats['why'].get(why, 0) + 1
+
+
+def device_zipup_step(VH_prev, B, W, explicit_plus_hc=False, finite=True):
+    """The matrix that an interior step of ``MPO.apply_zipup`` hands to ``svd_theta`` (reference mpo.py:1733, :1756-1757), labels
+    ``['(vL.p)', '(wR.vR)']`` with the pipes ``combine_legs([['vL', 'p'], ['wR', 'vR']], qconj=[+1, -1])`` builds, so that the
+    reference's ``U.split_legs()`` / ``VH.split_legs()`` work on the factors; or ``None`` where the route declines
+    (``_zipup_declines``, too many jobs) and the caller runs the generic statements.  ``VH_prev``: ``[vL, wR, vR]`` (the split ``VH`` of
+    the step before, scaled with S), ``B``: ``[vL, p, vR]``, ``W``: ``[wL, wR, p, p*]``.  One GEMM over chi (``T1 = VH_prev . B``, the
+    plan cache of ``tensordot``) and the MPO step of ``MpoZipupPlan``; operands are converted to ``result_type(B, W)`` first (a real
+    MPS meets a complex U on the first step)."""
+    why = _zipup_declines(VH_prev, B, W, explicit_plus_hc, finite)
+    if why is not None:
+        _zipup_decline(why)
+        return None
+    dtype = np.result_type(VH_prev.dtype, B.dtype, W.dtype)
+    VH_prev, B = (t if t.dtype == dtype else t.astype(dtype) for t in (VH_prev, B))
+    if list(VH_prev.get_leg_labels()) != ['vL', 'wR', 'vR']:
+        VH_prev = VH_prev.transpose(['vL', 'wR', 'vR'])
+    if list(B.get_leg_labels()) != ['vL', 'p', 'vR']:
+        B = B.transpose(['vL', 'p', 'vR'])
+    if list(W.get_leg_labels()) != ['wL', 'wR', 'p', 'p*']:
+        W = W.transpose(['wL', 'wR', 'p', 'p*'])
+    T1 = npc.tensordot(VH_prev, B, axes=['vR', 'vL'])        # vL, wR, p, vR
+    if T1.stored_blocks == 0:
+        _zipup_decline('empty tensor')
+        return None
+    try:
+        plan = MpoZipupPlan.get(T1, W)
+        if plan.empty:
+            _zipup_decline('empty tensor')
+            return None
+        if getattr(plan, '_counted', None) is None:
+            zipup_stats['plans_built'] += 1
+            plan._counted = True
+        M = plan.apply(T1)
+    except ExpandJobLimit:
+        _zipup_decline('too many jobs')
+        return None
+    zipup_stats['device_steps'] += 1
+    return M
 
 
 def _envs_wide(LP, RP):

@@ -8,7 +8,9 @@
 //  * tpa_lincomb_batch / tpa_mpo_apply_batch / tpa_mpo_entry_apply_batch: the MPO step of the factored effective Hamiltonians
 //                          (block combinations, small matrices on the physical index, single entries); tpa_mpo_expand_batch: the
 //                          entry-by-entry step with a destination offset per row -- the expanded matrix of the subspace expansion
-//                          of single-site DMRG in one pass (reference mps_common.py:2140-2168, :2170-2199).
+//                          of single-site DMRG in one pass (reference mps_common.py:2140-2168, :2170-2199); tpa_mpo_cell_apply_batch:
+//                          a cell of that matrix as one small dense product, every source row loaded once -- the zip-up application
+//                          of an MPO that is dense in the bond index (reference mpo.py:1733-1757).
 //  * tpa_scale_axis_batch: iscale_axis (np_conserved.py:2132-2140).
 //  * tpa_gather_axis_batch: iproject's np.compress along one axis (np_conserved.py:1982).
 #include "tpa_common.h"
@@ -337,6 +339,138 @@ __global__ __launch_bounds__(NT) void mpo_expand_kernel(const EntJob *__restrict
     mpo_entry_block<CPLX, VEC, ScatteredRows>(jobs, rows, terms, src, src2, dst);
 }
 
+// ---- a cell of the fused matrix as ONE small dense product: dst rows (n_rows) = coeff (n_rows x n_src) . distinct source rows (n_src) ---
+// What it replaces: tensordot(B, W) and combine_legs of the zip-up MPO application (reference mpo.py:1733-1757) for MPO tensors that are
+// DENSE in the bond index (the time-evolution MPOs U_I / U_II fill nearly every (wL, wR) block).  mpo_entry_job above computes every
+// destination row from its own term list: the N rows of a cell that draw on the same K source rows load each of them N times (N K
+// loads per column item).  Here a thread loads each source item ONCE and updates the accumulators of all rows of the job: K loads and
+// N stores per column item.
+//   item, thread, grid, access widths: those of mpo_expand_kernel (a thread owns one column item (i, j) of its job, lanes along j; 16
+//              bytes per item where the bases and, for real data, every offset and stride of the job allow it, decided per job).
+//   rows     : R = 8, 16 or 32 accumulators (selected by max_rows) in an array indexed by fully unrolled constants only -- registers,
+//              never scratch.  Accumulators o >= n_rows are not stored (cell_update).
+//   coeff    : the address of coeff(o, k) does not depend on the lane and is contiguous in o for a fixed k: UNIFORM (scalar) loads
+//              through the constant cache, no LDS; the job's matrix is shared by all wavefronts of the launch through that cache.
+//              The scalar register file does not hold the coefficients of four sources for 16 or 32 rows: the compiler spills scalar
+//              registers through vector lanes (counts with the register figures in DESIGN.md; cell_update says what was done about it).
+//   sources  : k ascending, the loads of four k issued before their multiply-adds; one chain of fused multiply-adds per component in
+//              table order, zero coefficients included, the complex pattern of ent_fma: on finite data the result equals what
+//              mpo_expand_kernel gives for the nonzero coefficients in the same order.
+struct CellJob {  // int64[10]
+    int64_t dst_off, pre, n_rows, post, dst_ld, row_begin, src_begin, n_src, coeff_off, pad;
+};
+struct CellRow {  // int64[2]
+    int64_t dst_row_off, pad;
+};
+struct CellSrc {  // int64[2]
+    int64_t src_off, src_ld;
+};
+
+constexpr int CELL_CHUNK = 8;
+
+// acc[o] += coeff(o, k) * v for the rows of the job.  Accumulators o >= n_rows are not stored.
+//   real   : CELL_CHUNK rows at a time behind a uniform branch -- a chunk inside the job reads its coefficients as one contiguous run
+//            from one base address, the chunk that holds the last row clamps the index, the chunks beyond it are skipped.  Without the
+//            branches the clamped addresses of all R rows stay live next to the coefficients of four sources and spill through vector
+//            lanes (R = 32: 1759 spilled scalar registers against 194 this way); measured at chi = 1024, 12- and 24-row cells: 0.086
+//            against 0.106 ms and 0.28 against 0.53 ms.
+//   complex: all R rows with the index clamped (the rows beyond the job repeat the last one), no branch: it spills less to begin with
+//            (at most 265), and the chunked form needs more vector registers and was slower on 1- to 12-row cells (0.047 against 0.038
+//            ms, 0.175 against 0.167 ms) and 6 % faster on 24-row cells only.
+template <bool CPLX, bool VEC, int R>
+__device__ __forceinline__ void cell_update(double2 (&acc)[R], const double *__restrict__ c, const int n_rows, const double2 v) {
+    constexpr int CW = CPLX ? 2 : 1;
+    const int last = n_rows - 1;
+    if constexpr (CPLX) {
+#pragma unroll
+        for (int o = 0; o < R; ++o) {
+            const int oc = o < last ? o : last;
+            const LinTerm t{0, 0, c[CW * oc], c[CW * oc + 1]};
+            ent_fma<CPLX, VEC>(acc[o], t, v);
+        }
+    } else {
+#pragma unroll
+        for (int o0 = 0; o0 < R; o0 += CELL_CHUNK) {
+            if (o0 + CELL_CHUNK <= n_rows) {
+#pragma unroll
+                for (int o = o0; o < o0 + CELL_CHUNK; ++o) ent_fma<CPLX, VEC>(acc[o], LinTerm{0, 0, c[o], 0.}, v);
+            } else if (o0 < n_rows) {
+#pragma unroll
+                for (int o = o0; o < o0 + CELL_CHUNK; ++o) ent_fma<CPLX, VEC>(acc[o], LinTerm{0, 0, c[o < last ? o : last], 0.}, v);
+            }
+        }
+    }
+}
+
+template <bool CPLX, bool VEC, int R>
+__device__ __forceinline__ void mpo_cell_job(const CellJob &J, const int n_store, const CellRow *__restrict__ rows,
+                                             const CellSrc *__restrict__ S, const double *__restrict__ coeff,
+                                             const double *__restrict__ src, double *__restrict__ dst) {
+    constexpr int EPI = (!CPLX && VEC) ? 2 : 1;        // elements per item
+    constexpr int CW = CPLX ? 2 : 1;                   // doubles per element
+    const int n_rows = (int)J.n_rows, ns = (int)J.n_src;
+    const int64_t post_items = J.post / EPI;
+    const int64_t n_cols = J.pre * post_items;
+    const double *C = coeff + CW * J.coeff_off;
+    const int64_t cs = (int64_t)CW * n_rows;           // doubles from the coefficients of source k to those of source k + 1
+    for (int64_t e = (int64_t)blockIdx.x * NT + threadIdx.x; e < n_cols; e += (int64_t)gridDim.x * NT) {
+        const int64_t i = e / post_items, j = (e - i * post_items) * EPI;
+        const double *x0 = src + CW * j;
+        double2 acc[R];
+#pragma unroll
+        for (int o = 0; o < R; ++o) acc[o] = double2{0., 0.};
+        int k = 0;
+        for (; k + 4 <= ns; k += 4) {
+            const double2 v0 = ent_load<CPLX, VEC>(x0 + CW * (S[k].src_off + i * S[k].src_ld));
+            const double2 v1 = ent_load<CPLX, VEC>(x0 + CW * (S[k + 1].src_off + i * S[k + 1].src_ld));
+            const double2 v2 = ent_load<CPLX, VEC>(x0 + CW * (S[k + 2].src_off + i * S[k + 2].src_ld));
+            const double2 v3 = ent_load<CPLX, VEC>(x0 + CW * (S[k + 3].src_off + i * S[k + 3].src_ld));
+            cell_update<CPLX, VEC, R>(acc, C + k * cs, n_rows, v0);
+            cell_update<CPLX, VEC, R>(acc, C + (k + 1) * cs, n_rows, v1);
+            cell_update<CPLX, VEC, R>(acc, C + (k + 2) * cs, n_rows, v2);
+            cell_update<CPLX, VEC, R>(acc, C + (k + 3) * cs, n_rows, v3);
+        }
+        for (; k < ns; ++k)
+            cell_update<CPLX, VEC, R>(acc, C + k * cs, n_rows, ent_load<CPLX, VEC>(x0 + CW * (S[k].src_off + i * S[k].src_ld)));
+        double *y = dst + CW * (J.dst_off + i * J.dst_ld + j);
+#pragma unroll
+        for (int o = 0; o < R; ++o) {
+            if (o < n_store) {
+                double *yo = y + CW * rows[o].dst_row_off;
+                if (VEC) {
+                    *reinterpret_cast<double2 *>(yo) = acc[o];
+                } else {
+                    yo[0] = acc[o].x;
+                    if (CPLX) yo[1] = acc[o].y;
+                }
+            }
+        }
+    }
+}
+
+template <bool CPLX, bool VEC, int R>
+__global__ __launch_bounds__(NT) void mpo_cell_kernel(const CellJob *__restrict__ jobs, const CellRow *__restrict__ rows,
+                                                      const CellSrc *__restrict__ srcs, const double *__restrict__ coeff, const int max_rows,
+                                                      const double *__restrict__ src, double *__restrict__ dst) {
+    const CellJob J = jobs[blockIdx.y];
+    if (J.pre <= 0 || J.n_rows <= 0 || J.post <= 0) return;
+    if ((int64_t)blockIdx.x * NT >= J.pre * J.post) return;      // the grid is sized by the largest job: nothing left for this workgroup
+    const CellRow *Rw = rows + J.row_begin;
+    const CellSrc *S = srcs + J.src_begin;
+    const int n_store = J.n_rows < max_rows ? (int)J.n_rows : max_rows;      // (max_rows <= R: rows beyond it are not written)
+    if (VEC && !CPLX) {         // two real elements per item: every address of the job has to stay on a 16-byte boundary
+        bool even = ((J.post | J.dst_off | J.dst_ld) & 1) == 0;
+        // every wavefront scans the tables of the job, lane l the entries l, l + 64, ...: the same answer in all of them
+        for (int64_t o = threadIdx.x & 63; o < n_store; o += 64) even = even && (Rw[o].dst_row_off & 1) == 0;
+        for (int64_t k = threadIdx.x & 63; k < J.n_src; k += 64) even = even && ((S[k].src_off | S[k].src_ld) & 1) == 0;
+        if (!__all(even)) {
+            mpo_cell_job<CPLX, false, R>(J, n_store, Rw, S, coeff, src, dst);
+            return;
+        }
+    }
+    mpo_cell_job<CPLX, VEC, R>(J, n_store, Rw, S, coeff, src, dst);
+}
+
 struct ScaleJob {  // int64[6]
     int64_t x_off, pre, len, post, s_off, pad;
 };
@@ -583,6 +717,52 @@ extern "C" int tpa_mpo_expand_batch(int dtype, const int64_t *jobs_dev, int n_jo
             mpo_expand_kernel<true, true><<<grid, NT, 0, st>>>(jobs, rows, terms, src, src2, dst);
         else
             mpo_expand_kernel<true, false><<<grid, NT, 0, st>>>(jobs, rows, terms, src, src2, dst);
+    }
+    TPA_LAUNCH_CHECK();
+    return 0;
+}
+
+template <bool CPLX, bool VEC>
+static void mpo_cell_launch(int max_rows, dim3 grid, hipStream_t st, const int64_t *jobs_dev, const int64_t *rows_dev, const int64_t *srcs_dev,
+                            const void *coeff_dev, const void *src_base, void *dst_base) {
+    const CellJob *jobs = (const CellJob *)jobs_dev;
+    const CellRow *rows = (const CellRow *)rows_dev;
+    const CellSrc *srcs = (const CellSrc *)srcs_dev;
+    const double *coeff = (const double *)coeff_dev, *src = (const double *)src_base;
+    double *dst = (double *)dst_base;
+    if (max_rows <= 8)
+        mpo_cell_kernel<CPLX, VEC, 8><<<grid, NT, 0, st>>>(jobs, rows, srcs, coeff, max_rows, src, dst);
+    else if (max_rows <= 16)
+        mpo_cell_kernel<CPLX, VEC, 16><<<grid, NT, 0, st>>>(jobs, rows, srcs, coeff, max_rows, src, dst);
+    else
+        mpo_cell_kernel<CPLX, VEC, 32><<<grid, NT, 0, st>>>(jobs, rows, srcs, coeff, max_rows, src, dst);
+}
+
+extern "C" int tpa_mpo_cell_apply_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const int64_t *rows_dev, const int64_t *srcs_dev,
+                                        const void *coeff_dev, int max_rows, int64_t max_job_cols, const void *src_base, void *dst_base,
+                                        void *stream) {
+    static_assert(TPA_MPO_CELL_MAXROWS == 32, "mpo_cell_launch dispatches up to 32 accumulators");
+    TPA_ARG_CHECK(dtype == TPA_F64 || dtype == TPA_C128);
+    TPA_ARG_CHECK(max_rows >= 1 && max_rows <= TPA_MPO_CELL_MAXROWS);
+    if (n_jobs <= 0) return 0;
+    TPA_ARG_CHECK(n_jobs <= 65535);
+    const bool aligned = (((uintptr_t)src_base | (uintptr_t)dst_base) & 15) == 0;
+    const int64_t items = (dtype == TPA_F64 && aligned) ? (max_job_cols + 1) / 2 : max_job_cols;
+    int64_t g = (items + NT - 1) / NT;
+    if (g < 1) g = 1;
+    if (g > 512) g = 512;
+    dim3 grid((int)g, n_jobs);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == TPA_F64) {
+        if (aligned)
+            mpo_cell_launch<false, true>(max_rows, grid, st, jobs_dev, rows_dev, srcs_dev, coeff_dev, src_base, dst_base);
+        else
+            mpo_cell_launch<false, false>(max_rows, grid, st, jobs_dev, rows_dev, srcs_dev, coeff_dev, src_base, dst_base);
+    } else {
+        if (aligned)
+            mpo_cell_launch<true, true>(max_rows, grid, st, jobs_dev, rows_dev, srcs_dev, coeff_dev, src_base, dst_base);
+        else
+            mpo_cell_launch<true, false>(max_rows, grid, st, jobs_dev, rows_dev, srcs_dev, coeff_dev, src_base, dst_base);
     }
     TPA_LAUNCH_CHECK();
     return 0;

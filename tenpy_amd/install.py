@@ -110,6 +110,10 @@ def use_fused_callers():
       DMRG is one GEMM over chi and one ``tpa_mpo_expand_batch`` launch (``mixer.device_expand_1site``; ``LHeff`` / ``RHeff`` are not
       built), else -- ``combine=True``, ``explicit_plus_hc``, infinite systems, sites the device class hands back -- the reference's
       method runs (``module_form.stats['expand_device']`` / ``['expand_reference']``).
+    * ``MPO.apply_zipup`` (``networks/mpo.py:1679``; ``MPO.apply`` with ``compression_method='zip_up'``, ``ExpMPOEvolution``) is wrapped in
+      place: the matrix of every interior site is one GEMM over chi and the MPO step on the device (``mps_common.device_zipup_step``,
+      ``tpa_mpo_cell_apply_batch`` / ``tpa_mpo_expand_batch``), the boundary sites and declined sites run the reference's statements
+      (``module_form.stats['zipup_device']`` / ``['zipup_reference']``, reasons in ``mps_common.zipup_stats['why']``).
     * ``TEBDEngine.evolve_step`` (``tebd.py:374``; inherited by ``QRBasedTEBDEngine``) -> the bonds of a half-step decomposed in one
       batched device call (``module_form.batched_tebd_evolve_step``; the per-bond statements stay the reference's).
     * ``LanczosEvolution`` (``linalg/krylov_based.py:718``; constructed at ``tdvp.py:132 _krylov_evolve``) -> the device class: the
@@ -151,6 +155,9 @@ def use_fused_callers():
     if not getattr(ref_mc.SubspaceExpansion.mix_and_decompose_1site, '_tpa_wrapped', False):
         ref_mc.SubspaceExpansion.mix_and_decompose_1site = module_form.device_subspace_expansion(
             ref_mc.SubspaceExpansion.mix_and_decompose_1site, ref_mc)
+    import tenpy.networks.mpo as ref_mpo
+    if not getattr(ref_mpo.MPO.apply_zipup, '_tpa_wrapped', False):
+        ref_mpo.MPO.apply_zipup = module_form.device_apply_zipup(ref_mpo.MPO.apply_zipup, ref_mpo)
     import tenpy.algorithms.tebd as ref_tebd
     if not getattr(ref_tebd.TEBDEngine.evolve_step, '_tpa_wrapped', False):
         ref_tebd.TEBDEngine.evolve_step = module_form.batched_tebd_evolve_step(ref_tebd)

@@ -1654,6 +1654,7 @@ def clear_device_caches():
         _mc.MpoBlockApplyPlan._cache.clear()
         _mc.MpoEntryApplyPlan._cache.clear()
         _mc.MpoExpandPlan._cache.clear()
+        _mc.MpoZipupPlan._cache.clear()
         _mc._skip_table_cache.clear()
     except ImportError:      # (the linalg package is importable on its own)
         pass

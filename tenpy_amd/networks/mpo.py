@@ -32,6 +32,67 @@ class MPO:
     def chi(self):
         return [W.get_leg('wL').ind_len for W in self._W] + [self._W[-1].get_leg('wR').ind_len]
 
+    def _zipup_IdL(self, i):
+        """Index of the "only identities to the left" state on the bond left of site i (one number for all bonds, or one per bond)."""
+        Id = self.IdL[i] if isinstance(self.IdL, (list, tuple)) else self.IdL
+        return Id % self._W[i].get_leg('wL').ind_len
+
+    def _zipup_IdR(self, i):
+        """Index of the "only identities to the right" state on the bond right of site i."""
+        Id = self.IdR[i + 1] if isinstance(self.IdR, (list, tuple)) else self.IdR
+        return Id % self._W[i].get_leg('wR').ind_len
+
+    def apply(self, psi, options):
+        """Apply the MPO to ``psi`` in place and compress it (reference mpo.py:1562-1609): ``compression_method='zip_up'`` is the one
+        method served -- ``apply_zipup``, then ``psi.compress_svd(trunc_params)``.  Returns the summed truncation error."""
+        method = options['compression_method']
+        if method != 'zip_up':
+            raise ValueError("compression_method %r is not served: this driver serves 'zip_up'" % (method,))
+        trunc_err = self.apply_zipup(psi, options)
+        return trunc_err + psi.compress_svd(options['trunc_params'])
+
+    def apply_zipup(self, psi, options):
+        """One left-to-right pass of the zip-up method (reference mpo.py:1679-1767): every site's ``W . B`` with the ``VH`` of the site
+        before is decomposed with the relaxed truncation ``chi_max * m_temp`` (``svd_min * trunc_weight``).  Interior sites build their
+        matrix by ``mps_common.device_zipup_step`` (one GEMM over chi and the MPO step on the device); the two boundary sites, and
+        interior sites the device route declines, run the reference's statements.  ``psi`` is afterwards only approximately canonical
+        (``apply`` compresses it).  Options: ``trunc_params``, ``m_temp`` (2), ``trunc_weight`` (1.).  Returns the truncation error;
+        ``psi.norm`` is updated."""
+        from ..algorithms.mps_common import device_zipup_step
+        from ..linalg.truncation import TruncationError, svd_theta
+        m_temp, trunc_weight = int(options.get('m_temp', 2)), float(options.get('trunc_weight', 1.))
+        relax_trunc = dict(options['trunc_params'])
+        relax_trunc['chi_max'] *= m_temp
+        if 'svd_min' in relax_trunc:
+            relax_trunc['svd_min'] *= trunc_weight
+        if psi.L != self.L:
+            raise ValueError('Length of MPS and MPO not the same')
+        if self.explicit_plus_hc:
+            raise NotImplementedError("Can't use explicit_plus_hc with apply_zipup")
+        trunc_err = TruncationError()
+        VH = None
+        for i in range(psi.L):
+            W, last = self.get_W(i), i == psi.L - 1
+            M = device_zipup_step(VH, psi.get_B(i, 'B'), W) if 0 < i and not last else None
+            if M is None:
+                M = npc.tensordot(psi.get_B(i, 'B'), W, axes=('p', 'p*'))
+                if i == 0:
+                    M = M.take_slice(self._zipup_IdL(i), 'wL')
+                else:
+                    M = npc.tensordot(VH, M, axes=(['wR', 'vR'], ['wL', 'vL']))
+                if last:
+                    M = M.take_slice(self._zipup_IdR(i), 'wR').combine_legs(['vL', 'p'], qconj=[-1])
+                else:
+                    M = M.combine_legs([['vL', 'p'], ['wR', 'vR']], qconj=[+1, -1])
+            U, S, VH, err, norm_new = svd_theta(M, relax_trunc, [M.qtotal, None] if last else [None, None])
+            trunc_err = trunc_err + err
+            psi.norm *= norm_new
+            if not last:
+                VH = VH.split_legs().iscale_axis(S, 'vL')
+            psi.set_SR(i, S)
+            psi.set_B(i, U.split_legs(), 'A')
+        return trunc_err
+
 
 def mpo_from_dense(W_dense_list, p_legs, chinfo, dtype=np.float64, IdL=0, IdR=-1, explicit_plus_hc=False):
     """Build a finite MPO from dense ``W[i]`` of shape (D_l, D_r, d, d).  The charges of the virtual MPO legs are deduced

@@ -140,6 +140,27 @@ class MPS:
             res.append(float(-np.sum(p * np.log(p))))
         return np.array(res)
 
+    def compress_svd(self, trunc_par):
+        """Compress in place with one sweep of QRs from the left end to the right one, without truncation, and one sweep of truncating
+        SVDs back (reference mps.py:5895-5933, finite chains); ``MPO.apply`` calls it after the zip-up pass.  Returns the truncation
+        error; ``norm`` is updated."""
+        from ..linalg.truncation import TruncationError, svd_theta
+        trunc_err = TruncationError()
+        B = self.get_B(0, 'Th')
+        for i in range(self.L - 1):
+            q, r = npc.qr(B.combine_legs(['vL', 'p']), inner_labels=['vR', 'vL'])
+            self.set_B(i, q.split_legs(), form=None)
+            B = npc.tensordot(r, self.get_B(i + 1, 'B'), axes=('vR', 'vL'))
+        for i in range(self.L - 1, 0, -1):
+            U, S, VH, err, norm_new = svd_theta(B.combine_legs(['p', 'vR']), trunc_par)
+            trunc_err = trunc_err + err
+            self.norm *= norm_new
+            self.set_B(i, VH.split_legs(), form='B')
+            B = npc.tensordot(self.get_B(i - 1, None), U, axes=('vR', 'vL')).iscale_axis(S, 'vR')
+            self.set_SL(i, S)
+        self.set_B(0, B, form='Th')
+        return trunc_err
+
     def norm_test(self):
         """<psi|psi> by contracting the transfer matrices (device tensordots)."""
         B = self.get_B(0, 'B')
