@@ -195,9 +195,7 @@ class TwoSiteDMRGEngine:
             eff_H = _plus_hc(eff_H)
         if not self.shard_matvec:
             # the contraction plans of this bond's previous visit (same block structure once chi has saturated: checked by their keys)
-            cache = self.__dict__.setdefault('_heff_plans', {})
-            if eff_H.factored and cache.get(i0) is not None:
-                eff_H._fplans = cache[i0]
+            eff_H.adopt_plans(self.__dict__.setdefault('_heff_plans', {}).get(i0))
         theta = eff_H.combine_theta(psi.get_theta(i0, n=2))
         self.eff_H = eff_H                                    # (the mixer looks at the operator itself, not at the projected one)
         if self.mixer is not None:
@@ -213,8 +211,9 @@ class TwoSiteDMRGEngine:
             E0, theta, N = lanczos_row_panels(eff_H, theta, self.lanczos_params)
         else:
             E0, theta, N = LanczosGroundState(eff_H, theta, self.lanczos_params).run()
-        if not self.shard_matvec and isinstance(getattr(eff_H, '_fplans', None), dict) and 'lkey' in eff_H._fplans:
-            self._heff_plans[i0] = eff_H._fplans
+        kept = None if self.shard_matvec else eff_H.plans_to_keep()
+        if kept is not None:
+            self._heff_plans[i0] = kept
         theta = eff_H.prepare_svd(theta)                      # fused matrix [(vL.p0), (p1.vR)]
         self._tick('lanczos')
         previous = npc.SVD_DIST_GROUP
@@ -357,8 +356,7 @@ class SingleSiteDMRGEngine(TwoSiteDMRGEngine):
         self._tick(None)
         eff_H = plain = OneSiteH(env, i0, combine=False, move_right=move_right)
         cache = self.__dict__.setdefault('_heff_plans', {})
-        if eff_H.factored and cache.get(i0) is not None:      # the plans of this site's previous visit (validated by their keys)
-            eff_H._fplans = cache[i0]
+        plain.adopt_plans(cache.get(i0))                      # the plans of this site's previous visit (validated by their keys)
         plain._expandplans = self.__dict__.setdefault('_expand_plans', {}).setdefault(i0, {})
         if getattr(self.H, 'explicit_plus_hc', False):
             eff_H = _plus_hc(eff_H)
@@ -366,8 +364,9 @@ class SingleSiteDMRGEngine(TwoSiteDMRGEngine):
         self.eff_H = plain                                    # (the mixer looks at the plain operator)
         self._tick('heff')
         E0, theta, N = LanczosGroundState(eff_H, theta, self.lanczos_params).run()
-        if isinstance(getattr(plain, '_fplans', None), dict) and 'lkey' in plain._fplans:
-            cache[i0] = plain._fplans
+        kept = plain.plans_to_keep()
+        if kept is not None:
+            cache[i0] = kept
         theta = self.prepare_svd(theta, move_right)
         self._tick('lanczos')
         U, S, VH, err = self.mixed_svd(theta, i0, move_right)

@@ -1181,18 +1181,52 @@ def factored_matvec_possible(LP, RP, W0, W1):
             w0 in (['wL', 'wR', 'p0', 'p0*'], ['wL', 'wR', 'p', 'p*']) and w1 in (['wL', 'wR', 'p1', 'p1*'], ['wL', 'wR', 'p', 'p*']))
 
 
-def _gemm_ops(plan, a_slot, b_slot, c_slot, bufs, scratch_name):
-    """Rows of a `tpa_lanczos_run` program for one planned contraction: the grouped GEMM, or -- split-K plans, `npc._split_k` --
-    the GEMM of the partial blocks into a scratch arena (appended to ``bufs``) followed by their reduction into ``c_slot``
-    (kind 1 with cfg = 1: timed together with the GEMM it completes)."""
-    sk = plan.sk
-    if sk is None:
-        return [[0, plan.cfg, plan.tasks_dev.data_ptr(), plan.links_dev.data_ptr(), plan.tiles_dev.data_ptr(), plan.n_tiles,
-                 a_slot, b_slot, c_slot, 0, 0, 0]]
-    bufs.append(dev.scratch(scratch_name, sk.total, plan.dtype))
-    part = len(bufs) - 1
-    return [[0, plan.cfg, sk.tasks_dev.data_ptr(), sk.links_dev.data_ptr(), sk.tiles_dev.data_ptr(), sk.n_tiles, a_slot, b_slot, part, 0, 0, 0],
-            [1, 1, sk.jobs_dev.data_ptr(), sk.terms_dev.data_ptr(), 0, sk.n_jobs, part, 0, c_slot, sk.max_elems, 0, 0]]
+class _Program:
+    """A launch program for ``tpa_lanczos_run`` (include/tenpy_amd.h) while it is put together: ``ops``, the rows ``(kind, cfg, p0, p1, p2,
+    count, a_slot, b_slot, c_slot, max_elems, 0, 0)``, and ``bufs``, the device tensors that the non-negative slots number (operands
+    first, then temporaries from the scratch pool, in the order they are asked for); slot -1 = input vector, -2 = output vector.
+    Apart from ``program_op`` of the MPO-step plans nothing else writes a row."""
+
+    def __init__(self, *operands):
+        self.bufs = list(operands)
+        self.ops = []
+
+    def scratch(self, name, n, dtype):
+        """The slot of a new temporary, the arena ``name`` of the scratch pool."""
+        self.bufs.append(dev.scratch(name, n, dtype))
+        return len(self.bufs) - 1
+
+    def gemm(self, plan, a, b, c, scratch_name, tiles=None, links=None, jobs=None, a2=None, alphas=None):
+        """One planned contraction: the grouped GEMM, or -- split-K plans, ``npc._split_k`` -- the GEMM of the partial blocks into a
+        scratch arena followed by their reduction into ``c`` (cfg = 1: timed together with the GEMM it completes).  In place of the
+        plan's own: ``tiles`` (fewer tiles), ``links``, ``jobs`` (the reduction of fewer blocks); with ``a2`` (a slot) and ``alphas``
+        the GEMM is kind 7, ``tpa_gemm_chain_ex``."""
+        sk = plan.sk
+        t = plan if sk is None else sk
+        tiles, n_tiles = (t.tiles_dev, t.n_tiles) if tiles is None else (tiles, len(tiles))
+        out = c if sk is None else self.scratch(scratch_name, sk.total, plan.dtype)
+        self.ops.append([0 if a2 is None else 7, plan.cfg, t.tasks_dev.data_ptr(), (t.links_dev if links is None else links).data_ptr(),
+                         tiles.data_ptr(), n_tiles, a, b, out, 0 if a2 is None else a2, 0 if a2 is None else alphas.data_ptr(), 0])
+        if sk is not None:
+            jobs, n_jobs = (sk.jobs_dev, sk.n_jobs) if jobs is None else (jobs, len(jobs))
+            self.lincomb(jobs, n_jobs, sk.terms_dev, sk.max_elems, out, c, cfg=1)
+
+    def lincomb(self, jobs, n_jobs, terms, max_elems, a, c, cfg=0):
+        self.ops.append([1, cfg, jobs.data_ptr(), terms.data_ptr(), 0, n_jobs, a, 0, c, max_elems, 0, 0])
+
+    def mpo_step(self, plan, a, c):
+        self.ops.append(plan.program_op(a, c))
+
+    def copy(self, jobs, n_jobs, max_elems, a, c):
+        self.ops.append([2, 0, jobs.data_ptr(), 0, 0, n_jobs, a, 0, c, max_elems, 0, 0])
+
+    def collective(self, a, c):
+        self.ops.append([3, 0, 0, 0, 0, 0, a, 0, c, 0, 0, 0])
+
+    def finish(self, gemm_plans, collective=None):
+        """``(ops, bufs, gemm_plans[, collective])``: what ``krylov_based._native_krylov`` takes."""
+        res = (np.array(self.ops, dtype=np.int64), self.bufs, gemm_plans)
+        return res if collective is None else res + (collective,)
 
 
 # The labels of an MPO step -- x_w, x_p, w_in, w_out, p_out, p_in of ``MpoApplyPlan`` -- going left to right (W0 on the legs wR, p0 of
@@ -1246,16 +1280,65 @@ def _factored_plans(LPf, RPf, theta, W0, W1=None, launch=False, old=None):
 
 
 class _DeviceEffectiveH:
-    """What the device forms of the effective Hamiltonians share: the hand-over of a vector to ``tpa_lanczos_run``.  A subclass
-    provides ``matvec_program(theta)`` (see :meth:`TwoSiteH.matvec_program`), which ends in :meth:`_file_program`."""
+    """What the device forms of the effective Hamiltonians share: the factored matvec over the plans of ``_factored_plans``, their
+    hand-over between the visits of a bond, and the hand-over of a vector to ``tpa_lanczos_run``.  A subclass provides
+    ``_build_program(theta)``."""
+
+    def _apply_factored(self, fp, theta):
+        """``LPf . theta`` (GEMM, contracted index = chi, not d chi), the MPO tensors applied blockwise (none without a site), ``. RPf``
+        (GEMM, chain over wR and the bond sector), by the plans ``fp``."""
+        T = fp['p1'].apply(self._LPf, theta)
+        step = fp.get('a01', fp.get('a0'))
+        if step is not None:
+            T = step.apply(T)
+        return fp['p2'].apply(T, self._RPf)
+
+    def adopt_plans(self, plans):
+        """Take the plans that :meth:`plans_to_keep` gave on the previous visit of this bond (used only while their keys match)."""
+        if self.factored and plans is not None:
+            self._fplans = plans
+
+    def plans_to_keep(self):
+        """The plans to hand to the next visit of this bond: a complete result of ``_factored_plans``, or ``None``."""
+        fp = getattr(self, '_fplans', None)
+        return fp if isinstance(fp, dict) and 'lkey' in fp else None
+
+    def _set_counts(self, p1, p2, mpo_bytes=0):
+        """The flop and byte counts of a matvec whose GEMM steps are ``p1`` and ``p2`` (they stay as they are where one is empty)."""
+        if not p1.empty and not p2.empty:
+            self.flops_per_matvec = p1.flops + p2.flops
+            self.bytes_per_matvec = p1.bytes_min + p2.bytes_min + mpo_bytes
+            self.gemm_shapes = (p1.gemm_shapes, p2.gemm_shapes)
+
+    def matvec_program(self, theta):
+        """The matvec as a replayable launch program for ``tpa_lanczos_run``: ``(ops, bufs, gemm_plans[, collective])`` (``_Program``).
+        ``None`` when the matvec cannot be replayed on raw arenas: vector not in the operator's own leg order, no plans, mixed
+        dtypes, or an output block structure different from the input's (the first steps from a product state, where H creates
+        blocks).  ``_build_program(theta)`` of the subclass gives ``(program, last plan of the chain)`` or ``None``."""
+        if list(theta.get_leg_labels()) != self.acts_on or theta.stored_blocks == 0 or not theta._is_packed():
+            return None
+        prog = self.__dict__.get('_program')
+        if prog is not None and prog[0] == (theta._struct_key(), theta.dtype):
+            return prog[1]
+        return self._file_program(theta, *(self._build_program(theta) or (None, None)))
+
+    @staticmethod
+    def _closed(theta, last):
+        """Whether the result of plan ``last`` has the block structure of ``theta``."""
+        return (last.res_total == theta._arena.numel() and np.array_equal(last.res_qdata, theta._qdata)
+                and np.array_equal(last.res_offsets, theta._offsets))
+
+    @staticmethod
+    def _replayable(theta, *parts):
+        """Whether the operands and plans ``parts`` have the dtype of ``theta`` and no plan among them is an empty step."""
+        return all(x.dtype == theta.dtype and not getattr(x, 'empty', False) for x in parts)
 
     def _file_program(self, theta, res, last):
         """Keep the program ``res`` of a contraction chain ending in plan ``last`` for ``theta``'s structure -- or, when the chain's
         output has another block structure than its input (no replay on raw arenas), that structure for :meth:`native_input`."""
         key = (theta._struct_key(), theta.dtype)
         self.__dict__['_program_out'] = None
-        if res is not None and not (last.res_total == theta._arena.numel() and np.array_equal(last.res_qdata, theta._qdata)
-                                    and np.array_equal(last.res_offsets, theta._offsets)):
+        if res is not None and not self._closed(theta, last):
             self.__dict__['_program_out'] = (key, last.res_qdata, last.res_offsets, last.res_total)
             res = None
         self.__dict__['_program'] = (key, res)
@@ -1315,7 +1398,7 @@ class TwoSiteH(_DeviceEffectiveH):
         # `explicit_plus_hc` whose operator runs as `PlusHcH`, the sharded subclass: the full program)
         self._skip_ok = tensors is None and not getattr(env.H, 'explicit_plus_hc', False)
         self._LHeff = self._RHeff = None
-        self._plans = None
+        self._fused = None          # (p1, p2, structure key, dtype) of the LHeff . theta . RHeff form
         self._fplans = None
         if factored is None:
             want = FACTORED_MATVEC and int(np.max(self.LP.get_leg('vR').get_block_sizes())) >= FACTORED_MIN_SECTOR
@@ -1421,13 +1504,9 @@ class TwoSiteH(_DeviceEffectiveH):
         return theta.combine_legs([['vL', 'p0'], ['p1', 'vR']], pipes=[self.pipeL, self.pipeR])
 
     def _matvec_factored(self, theta):
-        """theta [vL, p0, p1, vR] -> LP . theta . W0 W1 . RP with the same legs:
-        T1 = LP . theta (GEMM, contracted index = chi, not d chi);  T3 = MPO tensors applied blockwise (lincomb);
-        theta' = T3 . RP (GEMM, chain over wR and the bond sector)."""
-        fp, T3 = self._plans_for(theta, launch=True)
-        if T3 is None:              # plans that were there already; building them runs the first two steps
-            T3 = fp['a01'].apply(fp['p1'].apply(self._LPf, theta))
-        res = fp['p2'].apply(T3, self._RPf)
+        """theta [vL, p0, p1, vR] -> LP . theta . W0 W1 . RP with the same legs (``_apply_factored``)."""
+        fp, T3 = self._plans_for(theta, launch=True)      # (building the plans runs the first two steps)
+        res = self._apply_factored(fp, theta) if T3 is None else fp['p2'].apply(T3, self._RPf)
         res.iset_leg_labels(['vL', 'p0', 'p1', 'vR'])
         return res
 
@@ -1437,12 +1516,29 @@ class TwoSiteH(_DeviceEffectiveH):
         fp, _, T3 = _factored_plans(self._LPf, self._RPf, theta, self.W0, self.W1, launch, old=self._fplans)
         if fp is not None and fp is not self._fplans:
             self._fplans = fp
-            p1, p2 = fp['p1'], fp['p2']
-            if not p1.empty and not p2.empty:
-                self.flops_per_matvec = p1.flops + p2.flops
-                self.bytes_per_matvec = p1.bytes_min + p2.bytes_min + fp['a01'].bytes
-                self.gemm_shapes = (p1.gemm_shapes, p2.gemm_shapes)
+            self._set_counts(fp['p1'], fp['p2'], fp['a01'].bytes)
         return fp, T3
+
+    def _fused_plans(self, theta, launch):
+        """``(p1, p2, tmp)``: the plans of ``LHeff . theta`` and ``. RHeff`` as ``_fused`` keeps them, and the result of step 1 if they
+        were built now (else ``None``).  ``launch`` as in ``_factored_plans``: step 1 runs while they are built and a transposed
+        copy is an assertion failure; without it nothing is launched, and a transposed copy or an empty step means ``None``."""
+        if self._fused is not None and self._fused[2:] == (theta._struct_key(), theta.dtype):
+            return self._fused[0], self._fused[1], None
+        p1, l_use, t_use = npc.plan_tensordot(self.LHeff, theta, axes=['(vR.p0*)', '(vL.p0)'])
+        fits = l_use is self.LHeff and t_use is theta
+        assert fits or not launch, "matvec step 1 must not need a transpose"
+        if not fits or (p1.empty and not launch):
+            return None
+        tmp = p1.apply(self.LHeff, theta, launch=launch)
+        p2, t2_use, r_use = npc.plan_tensordot(tmp, self.RHeff, axes=(['wR', '(p1.vR)'], ['wL', '(p1*.vL)']))
+        fits = t2_use is tmp and r_use is self.RHeff
+        assert fits or not launch, "matvec step 2 must not need a transpose"
+        if not fits or (p2.empty and not launch):
+            return None
+        self._fused = (p1, p2, theta._struct_key(), theta.dtype)
+        self._set_counts(p1, p2)
+        return p1, p2, tmp
 
     def matvec(self, theta):
         """theta [(vL.p0), (p1.vR)] (fused mode) or [vL, p0, p1, vR] (factored mode) -> H_eff theta, same legs and labels."""
@@ -1450,81 +1546,43 @@ class TwoSiteH(_DeviceEffectiveH):
             if theta.rank == 2:      # a fused vector handed to a factored operator (tests, parity checks)
                 return self.prepare_svd(self._matvec_factored(self.combine_theta(theta)))
             return self._matvec_factored(theta)
-        if self._plans is None or not self._plan_matches(theta):
-            p1, l_use, t_use = npc.plan_tensordot(self.LHeff, theta, axes=['(vR.p0*)', '(vL.p0)'])
-            assert l_use is self.LHeff and t_use is theta, "matvec step 1 must not need a transpose"
-            tmp = p1.apply(self.LHeff, theta)
-            p2, t2_use, r_use = npc.plan_tensordot(tmp, self.RHeff, axes=(['wR', '(p1.vR)'], ['wL', '(p1*.vL)']))
-            assert t2_use is tmp and r_use is self.RHeff, "matvec step 2 must not need a transpose"
-            self._plans = (p1, p2, theta._struct_key(), theta.dtype)
-            if not p1.empty and not p2.empty:
-                self.flops_per_matvec = p1.flops + p2.flops
-                self.bytes_per_matvec = p1.bytes_min + p2.bytes_min
-                self.gemm_shapes = (p1.gemm_shapes, p2.gemm_shapes)
-            res = p2.apply(tmp, self.RHeff)
-        else:
-            p1, p2 = self._plans[0], self._plans[1]
-            tmp = p1.apply(self.LHeff, theta)
-            res = p2.apply(tmp, self.RHeff)
+        p1, p2, tmp = self._fused_plans(theta, launch=True)
+        res = p2.apply(p1.apply(self.LHeff, theta) if tmp is None else tmp, self.RHeff)
         res.iset_leg_labels(['(vL.p0)', '(p1.vR)'])
         return res
 
-    def matvec_program(self, theta):
-        """The matvec as a replayable launch program for ``tpa_lanczos_run`` (include/tenpy_amd.h): ``(ops, bufs)`` with ``ops``
-        int64 ``[n_ops, 12]`` rows ``(kind, cfg, p0, p1, p2, count, a_slot, b_slot, c_slot, max_elems, 0, 0)`` and ``bufs`` the
-        list of device tensors the non-negative slots refer to (operands first, then temporaries from the scratch pool);
-        slot -1 = input vector, -2 = output vector.  ``None`` when the matvec cannot be replayed on raw arenas: vector not
-        in the operator's own leg order, mixed dtypes, or an output block structure different from the input's (the first
-        steps from a product state, where H creates blocks)."""
-        want = ['vL', 'p0', 'p1', 'vR'] if self.factored else ['(vL.p0)', '(p1.vR)']
-        if list(theta.get_leg_labels()) != want or theta.stored_blocks == 0 or not theta._is_packed():
-            return None
-        key = (theta._struct_key(), theta.dtype)
-        prog = self.__dict__.get('_program')
-        if prog is not None and prog[0] == key:
-            return prog[1]
-        res = None
+    def _build_program(self, theta):
         if self.factored:
             fp = self._plans_for(theta, launch=False)[0]
             if fp is None:
                 return None
             p1, a01, p2 = fp['p1'], fp['a01'], fp['p2']
-            ok = (p1.dtype == a01.dtype == p2.dtype == theta.dtype == self._LPf.dtype == self._RPf.dtype and not p1.empty and
-                  not p2.empty and not a01.empty)
-            if ok:
-                res = self._skip_program(theta, fp)
-                last = p2
-            if ok and res is None:
-                bufs = [self._LPf._arena, self._RPf._arena, dev.scratch('lanczos_t1', p1.res_total, p1.dtype),
-                        dev.scratch('lanczos_t3', a01.total, a01.dtype)]
-                ops = _gemm_ops(p1, 0, -1, 2, bufs, 'lanczos_sk1')
-                ops.append(a01.program_op(2, 3))
-                ops += _gemm_ops(p2, 3, 1, -2, bufs, 'lanczos_sk2')
-                res = (np.array(ops, dtype=np.int64), bufs, (p1, p2))
-                last = p2
-        else:
-            if self._plans is None or not self._plan_matches(theta):
-                p1, l_use, t_use = npc.plan_tensordot(self.LHeff, theta, axes=['(vR.p0*)', '(vL.p0)'])
-                if l_use is not self.LHeff or t_use is not theta or p1.empty:
-                    return None
-                tmp = p1.apply(self.LHeff, theta, launch=False)
-                p2, t2_use, r_use = npc.plan_tensordot(tmp, self.RHeff, axes=(['wR', '(p1.vR)'], ['wL', '(p1*.vL)']))
-                if t2_use is not tmp or r_use is not self.RHeff or p2.empty:
-                    return None
-                self._plans = (p1, p2, theta._struct_key(), theta.dtype)
-                self.flops_per_matvec = p1.flops + p2.flops
-                self.bytes_per_matvec = p1.bytes_min + p2.bytes_min
-                self.gemm_shapes = (p1.gemm_shapes, p2.gemm_shapes)
-            p1, p2 = self._plans[0], self._plans[1]
-            if p1.dtype == p2.dtype == theta.dtype == self.LHeff.dtype == self.RHeff.dtype and not p1.empty and not p2.empty:
-                bufs = [self.LHeff._arena, self.RHeff._arena, dev.scratch('lanczos_t1', p1.res_total, p1.dtype)]
-                ops = _gemm_ops(p1, 0, -1, 2, bufs, 'lanczos_sk1') + _gemm_ops(p2, 2, 1, -2, bufs, 'lanczos_sk2')
-                res = (np.array(ops, dtype=np.int64), bufs, (p1, p2))
-                last = p2
-        return self._file_program(theta, res, last if res is not None else None)
+            if not self._replayable(theta, self._LPf, self._RPf, p1, a01, p2):
+                return None
+            res = self._skip_program(theta, fp)
+            if res is None:
+                prog = self._new_program(p1, a01)
+                prog.gemm(p1, 0, -1, 2, 'lanczos_sk1')
+                prog.mpo_step(a01, 2, 3)
+                prog.gemm(p2, 3, 1, -2, 'lanczos_sk2')
+                res = prog.finish((p1, p2))
+            return res, p2
+        plans = self._fused_plans(theta, launch=False)
+        if plans is None or not self._replayable(theta, self.LHeff, self.RHeff, *plans[:2]):
+            return None
+        p1, p2 = plans[:2]
+        prog = _Program(self.LHeff._arena, self.RHeff._arena)
+        prog.scratch('lanczos_t1', p1.res_total, p1.dtype)
+        prog.gemm(p1, 0, -1, 2, 'lanczos_sk1')
+        prog.gemm(p2, 2, 1, -2, 'lanczos_sk2')
+        return prog.finish((p1, p2)), p2
 
-    def _plan_matches(self, theta):
-        return self._plans[2] == theta._struct_key() and self._plans[3] == theta.dtype
+    def _new_program(self, p1, a01):
+        """A program of the factored form: LP, RP, T1 and T3 in slots 0 to 3."""
+        prog = _Program(self._LPf._arena, self._RPf._arena)
+        prog.scratch('lanczos_t1', p1.res_total, p1.dtype)
+        prog.scratch('lanczos_t3', a01.total, a01.dtype)
+        return prog
 
     # ---- the launch program without the work nobody reads (DESIGN 3.3) ----------------------------------------------------
     def _skip_program(self, theta, fp):
@@ -1545,8 +1603,7 @@ class TwoSiteH(_DeviceEffectiveH):
         ``krylov_based.skip_declined``."""
         from ..linalg import krylov_based as kb
         p1, a01, p2 = fp['p1'], fp['a01'], fp['p2']
-        if not MATVEC_SKIP or not (p2.res_total == theta._arena.numel() and np.array_equal(p2.res_qdata, theta._qdata) and
-                                   np.array_equal(p2.res_offsets, theta._offsets)):
+        if not MATVEC_SKIP or not self._closed(theta, p2):
             return None                     # (switched off; H creates blocks: `_file_program` keeps no program either way)
 
         def declined(reason):
@@ -1574,34 +1631,13 @@ class TwoSiteH(_DeviceEffectiveH):
         if isinstance(et, str):
             return declined(et)
         kb.stats['n_skip_taken'] += 1
-        bufs = [self._LPf._arena, self._RPf._arena, dev.scratch('lanczos_t1', p1.res_total, p1.dtype),
-                dev.scratch('lanczos_t3', a01.total, a01.dtype)]
-        if et['a_tiles'] is None:
-            ops = _gemm_ops(p1, 0, -1, 2, bufs, 'lanczos_sk1')
-        elif p1.sk is None:
-            ops = [[0, p1.cfg, p1.tasks_dev.data_ptr(), p1.links_dev.data_ptr(), et['a_tiles'].data_ptr(), len(et['a_tiles']), 0, -1, 2, 0, 0, 0]]
-        else:
-            sk = p1.sk
-            bufs.append(dev.scratch('lanczos_sk1', sk.total, p1.dtype))
-            ops = [[0, p1.cfg, sk.tasks_dev.data_ptr(), sk.links_dev.data_ptr(), et['a_tiles'].data_ptr(), len(et['a_tiles']), 0, -1,
-                    len(bufs) - 1, 0, 0, 0],
-                   [1, 1, et['a_jobs'].data_ptr(), sk.terms_dev.data_ptr(), 0, len(et['a_jobs']), len(bufs) - 1, 0, 2, sk.max_elems, 0, 0]]
+        prog = self._new_program(p1, a01)
+        prog.gemm(p1, 0, -1, 2, 'lanczos_sk1', tiles=et['a_tiles'], jobs=et['a_jobs'])
         if et['b_jobs'] is not None:
-            ops.append([1, 0, et['b_jobs'].data_ptr(), a01.terms_dev.data_ptr(), 0, len(et['b_jobs']), 2, 0, 3, a01.max_elems, 0, 0])
-        sk = p2.sk
-        if sk is None:
-            ops.append([7, p2.cfg, p2.tasks_dev.data_ptr(), et['c_links'].data_ptr(), p2.tiles_dev.data_ptr(), p2.n_tiles, 3, 1, -2, 2,
-                        et['alphas'].data_ptr(), 0])
-        else:
-            bufs.append(dev.scratch('lanczos_sk2', sk.total, p2.dtype))
-            part = len(bufs) - 1
-            ops.append([7, p2.cfg, sk.tasks_dev.data_ptr(), et['c_links'].data_ptr(), sk.tiles_dev.data_ptr(), sk.n_tiles, 3, 1, part, 2,
-                        et['alphas'].data_ptr(), 0])
-            ops.append([1, 1, sk.jobs_dev.data_ptr(), sk.terms_dev.data_ptr(), 0, sk.n_jobs, part, 0, -2, sk.max_elems, 0, 0])
-        self.flops_per_matvec = et['plan_a'].flops + p2.flops
-        self.bytes_per_matvec = et['plan_a'].bytes_min + p2.bytes_min + et['b_bytes']
-        self.gemm_shapes = (et['plan_a'].gemm_shapes, p2.gemm_shapes)
-        return (np.array(ops, dtype=np.int64), bufs, (et['plan_a'], p2))
+            prog.lincomb(et['b_jobs'], len(et['b_jobs']), a01.terms_dev, a01.max_elems, 2, 3)
+        prog.gemm(p2, 3, 1, -2, 'lanczos_sk2', links=et['c_links'], a2=2, alphas=et['alphas'])
+        self._set_counts(et['plan_a'], p2, et['b_bytes'])
+        return prog.finish((et['plan_a'], p2))
 
     @staticmethod
     def _skip_tables(fp):
@@ -1659,7 +1695,7 @@ class TwoSiteH(_DeviceEffectiveH):
                 _, ua = np.unique(p1.links_host[lk, 0], return_index=True)
                 _, ub = np.unique(p1.links_host[lk, 1], return_index=True)
                 from types import SimpleNamespace
-                plan_a = SimpleNamespace(flops=int(2 * np.sum(mt * kk * nt_)), gemm_shapes=np.stack([mt, kk, nt_], axis=1),
+                plan_a = SimpleNamespace(empty=False, flops=int(2 * np.sum(mt * kk * nt_)), gemm_shapes=np.stack([mt, kk, nt_], axis=1),
                                          bytes_min=int(8 * (np.sum(mt[ua] * kk[ua]) + np.sum(kk[ub] * nt_[ub]) + np.sum(t1[need, 1] * t1[need, 2]))))
                 if sk is None:
                     (et['a_tiles'],) = dev.to_device_packed(kept)
@@ -1779,10 +1815,7 @@ class _LocalH(_DeviceEffectiveH):
             theta = theta.transpose(self.acts_on)
         fp = self._plans(theta) if (self.factored and theta.stored_blocks > 0) else None
         if fp is not None:
-            T = fp['p1'].apply(self._LPf, theta)
-            if fp['a0'] is not None:
-                T = fp['a0'].apply(T)
-            res = fp['p2'].apply(T, self._RPf)
+            res = self._apply_factored(fp, theta)
         else:               # the reference's contractions (no blockwise form of the MPO step -- `_mpo_plan_class` --, empty theta)
             res = npc.tensordot(self.LP, theta, axes=['vR', 'vL'])
             if self.W0 is not None:
@@ -1792,30 +1825,22 @@ class _LocalH(_DeviceEffectiveH):
         res.iset_leg_labels(self.acts_on)
         return res if labels == self.acts_on else res.transpose(labels)
 
-    def matvec_program(self, theta):
-        """The matvec as a launch program for ``tpa_lanczos_run`` (format: :meth:`TwoSiteH.matvec_program`), or ``None``: no factored
-        form, vector not in the order of ``acts_on``, mixed dtypes, or an output block structure other than the input's."""
-        if not self.factored or list(theta.get_leg_labels()) != self.acts_on or theta.stored_blocks == 0 or not theta._is_packed():
+    def _build_program(self, theta):
+        fp = self._plans(theta) if self.factored else None
+        if fp is None:
             return None
-        key = (theta._struct_key(), theta.dtype)
-        prog = self.__dict__.get('_program')
-        if prog is not None and prog[0] == key:
-            return prog[1]
-        fp = self._plans(theta)
-        res = last = None
-        if fp is not None:
-            p1, a0, p2 = fp['p1'], fp['a0'], fp['p2']
-            if p1.dtype == p2.dtype == theta.dtype == self._LPf.dtype == self._RPf.dtype and (a0 is None or a0.dtype == theta.dtype):
-                bufs = [self._LPf._arena, self._RPf._arena, dev.scratch('lanczos_t1', p1.res_total, p1.dtype)]
-                ops = _gemm_ops(p1, 0, -1, 2, bufs, 'lanczos_sk1')
-                src = 2
-                if a0 is not None:
-                    bufs.append(dev.scratch('lanczos_t3', a0.total, a0.dtype))
-                    src = len(bufs) - 1
-                    ops.append(a0.program_op(2, src))
-                ops += _gemm_ops(p2, src, 1, -2, bufs, 'lanczos_sk2')
-                res, last = (np.array(ops, dtype=np.int64), bufs, (p1, p2)), p2
-        return self._file_program(theta, res, last)
+        p1, a0, p2 = fp['p1'], fp['a0'], fp['p2']
+        if not self._replayable(theta, self._LPf, self._RPf, *(p for p in (p1, a0, p2) if p is not None)):
+            return None
+        prog = _Program(self._LPf._arena, self._RPf._arena)
+        src = prog.scratch('lanczos_t1', p1.res_total, p1.dtype)
+        prog.gemm(p1, 0, -1, src, 'lanczos_sk1')
+        if a0 is not None:
+            t3 = prog.scratch('lanczos_t3', a0.total, a0.dtype)
+            prog.mpo_step(a0, src, t3)
+            src = t3
+        prog.gemm(p2, src, 1, -2, 'lanczos_sk2')
+        return prog.finish((p1, p2)), p2
 
     def adjoint(self):
         return AdjointH(self)
@@ -2085,14 +2110,12 @@ class PlusHcH:
     flops_per_matvec = property(lambda self: getattr(self.doubled, 'flops_per_matvec', None))
     bytes_per_matvec = property(lambda self: getattr(self.doubled, 'bytes_per_matvec', None))
 
-    @property
-    def _fplans(self):
+    def adopt_plans(self, plans):
         """The contraction plans a driver keeps from visit to visit of a bond: those of the doubled tensors."""
-        return self.doubled._fplans
+        self.doubled.adopt_plans(plans)
 
-    @_fplans.setter
-    def _fplans(self, value):
-        self.doubled._fplans = value
+    def plans_to_keep(self):
+        return self.doubled.plans_to_keep()
 
     def adjoint(self):
         return self

@@ -24,7 +24,7 @@ import numpy as np
 
 from ..linalg import _device as dev
 from ..linalg import np_conserved as npc
-from .mps_common import TwoSiteH, _gemm_ops
+from .mps_common import TwoSiteH, _Program
 
 __all__ = ['ShardedTwoSiteH', 'row_partition', 'restrict_plan_rows', 'lanczos_row_panels', 'RowPanelOps', 'ShardedTEBDEngine']
 
@@ -242,12 +242,9 @@ class ShardedTwoSiteH(TwoSiteH):
 
     def _matvec_sharded_factored(self, theta):
         if self._sharded is None or self._sharded['key'] != (theta._struct_key(), theta.dtype):
-            self._sharded = self._build_sharded_factored(theta)
+            self._use_sharded(self._build_sharded_factored(theta))
             if self._sharded is None:
                 return super().matvec(theta)
-            s = self._sharded
-            self.flops_per_matvec = s['p1'].flops + s['p2'].flops
-            self.bytes_per_matvec = s['p1'].bytes_min + s['p2'].bytes_min + s['a01'].bytes
         s = self._sharded
         self._mid(s)
         T1, T3 = s['T1'], s['T3']
@@ -311,20 +308,14 @@ class ShardedTwoSiteH(TwoSiteH):
         if n_up:
             dev.check(L.tpa_copy_batch(code, up.data_ptr(), n_up, mx_up, recv.data_ptr(), out_arena.data_ptr(), dev.stream()), "unpack")
 
-    def matvec_program(self, theta):
-        """The sharded matvec as a launch program for ``tpa_lanczos_run`` (round 4, VERDICT r3 task 5): the row-restricted GEMM plans of
-        this rank, the pack / unpack copies of the row panels (op kind 2) and the all-gather as the program's collective (op kind 3,
-        enqueued from the host callback on the launch stream), so that N > 1 runs the same single-call Lanczos as N = 1.  Returns
-        ``(ops, bufs, gemm_plans, collective)`` or ``None`` (the step-by-step loop with :meth:`matvec` is the fallback)."""
+    def _build_program(self, theta):
+        """The sharded matvec as a launch program for ``tpa_lanczos_run``: the row-restricted GEMM plans of this rank, the pack / unpack
+        copies of the row panels (op kind 2) and the all-gather as the program's collective (op kind 3, enqueued from the host
+        callback on the launch stream), so that N > 1 runs the same single-call Lanczos as N = 1.  The program is
+        ``(ops, bufs, gemm_plans, collective)``; without one the step-by-step loop with :meth:`matvec` is the fallback."""
         if self.world == 1 and not _forced():
-            return super().matvec_program(theta)
-        want = ['vL', 'p0', 'p1', 'vR'] if self.factored else ['(vL.p0)', '(p1.vR)']
-        if list(theta.get_leg_labels()) != want or theta.stored_blocks == 0 or not theta._is_packed():
-            return None
+            return super()._build_program(theta)
         key = (theta._struct_key(), theta.dtype)
-        prog = self.__dict__.get('_program')
-        if prog is not None and prog[0] == key:
-            return prog[1]
         if self._sharded is None or self._sharded['key'] != key:
             # tables of this bond's previous visits (`_sharded_cache`: a dictionary owned by the engine, keyed by the block structure of
             # the vector -- a bond whose theta has to be embedded in the structure of H theta asks twice per visit), valid while the
@@ -340,63 +331,50 @@ class ShardedTwoSiteH(TwoSiteH):
                     if len(cache) >= 4:
                         cache.clear()
                     cache[key] = s
-            self._sharded = s
-            if self._sharded is not None:
-                s = self._sharded
-                self.flops_per_matvec = s['p1'].flops + s['p2'].flops
-                self.bytes_per_matvec = s['p1'].bytes_min + s['p2'].bytes_min + (s['a01'].bytes if self.factored else 0)
+            self._use_sharded(s)
         s = self._sharded
-        res = None
-        self.__dict__['_program_out'] = None
-        if s is not None:
-            p2 = s['p2']
-            same = (p2.res_total == theta._arena.numel() and np.array_equal(p2.res_qdata, theta._qdata)
-                    and np.array_equal(p2.res_offsets, theta._offsets))
-            left, right = (self._LPf, self._RPf) if self.factored else (self.LHeff, self.RHeff)
-            if not same:
-                self.__dict__['_program_out'] = (key, p2.res_qdata, p2.res_offsets, p2.res_total)
-            elif p2.dtype == theta.dtype == left.dtype == right.dtype:
-                (pk, n_pk, mx_pk), (up, n_up, mx_up) = self._gather_jobs(s)
-                dt = p2.dtype
-                send = dev.scratch('shard_send', s['maxlen'], dt)
-                recv = dev.scratch('shard_recv', s['maxlen'] * self.world, dt)
-                mid = list(self._mid(s)) if self.factored else [s['tmp']._arena]
-                bufs = [left._arena, right._arena] + mid + [send, recv]
-                i_send, i_recv = len(bufs) - 2, len(bufs) - 1
-                ops = []
-                sp1, sp2 = s['sp1'], s['sp2']
-                if not sp1.local_empty:
-                    ops += _gemm_ops(sp1, 0, -1, 2, bufs, 'shard_sk1')
-                last_mid = 2
-                if self.factored:
-                    if s['n_lin']:
-                        ops.append([1, 0, s['lin_jobs'].data_ptr(), s['lin_terms'].data_ptr(), 0, s['n_lin'], 2, 0, 3, s['lin_max'], 0, 0])
-                    last_mid = 3
-                if not sp2.local_empty:
-                    ops += _gemm_ops(sp2, last_mid, 1, -2, bufs, 'shard_sk2')
-                if n_pk:
-                    ops.append([2, 0, pk.data_ptr(), 0, 0, n_pk, -2, 0, i_send, mx_pk, 0, 0])
-                ops.append([3, 0, 0, 0, 0, 0, i_send, 0, i_recv, 0, 0, 0])
-                if n_up:
-                    ops.append([2, 0, up.data_ptr(), 0, 0, n_up, i_recv, 0, -2, mx_up, 0, 0])
-                group, cplx = self.group, np.dtype(dt).kind == 'c'
+        left, right = (self._LPf, self._RPf) if self.factored else (self.LHeff, self.RHeff)
+        if s is None or not self._replayable(theta, left, right, s['p2']):
+            return None
+        (pk, n_pk, mx_pk), (up, n_up, mx_up) = self._gather_jobs(s)
+        dt = s['p2'].dtype
+        prog = _Program(left._arena, right._arena, *(self._mid(s) if self.factored else [s['tmp']._arena]))
+        i_send = prog.scratch('shard_send', s['maxlen'], dt)
+        i_recv = prog.scratch('shard_recv', s['maxlen'] * self.world, dt)
+        send, recv = prog.bufs[i_send], prog.bufs[i_recv]
+        if not s['sp1'].local_empty:
+            prog.gemm(s['sp1'], 0, -1, 2, 'shard_sk1')
+        if self.factored and s['n_lin']:
+            prog.lincomb(s['lin_jobs'], s['n_lin'], s['lin_terms'], s['lin_max'], 2, 3)
+        if not s['sp2'].local_empty:
+            prog.gemm(s['sp2'], 3 if self.factored else 2, 1, -2, 'shard_sk2')
+        if n_pk:
+            prog.copy(pk, n_pk, mx_pk, -2, i_send)
+        prog.collective(i_send, i_recv)
+        if n_up:
+            prog.copy(up, n_up, mx_up, i_recv, -2)
+        group, cplx = self.group, np.dtype(dt).kind == 'c'
 
-                def collective(which, user, send=send, recv=recv, group=group, cplx=cplx):
-                    try:
-                        if cplx:       # RCCL has no complex type: ship interleaved (re, im) doubles
-                            import torch
-                            _dist().all_gather_into_tensor(recv.view(torch.float64), send.view(torch.float64), group=group)
-                        else:
-                            _dist().all_gather_into_tensor(recv, send, group=group)
-                        return 0
-                    except BaseException:      # must not unwind through the C frame
-                        import traceback
-                        traceback.print_exc()
-                        return 1
-                collective.agree = lambda failed, group=group: _agree_failure(failed, group)
-                res = (np.array(ops, dtype=np.int64), bufs, (), collective)
-        self.__dict__['_program'] = (key, res)
-        return res
+        def collective(which, user, send=send, recv=recv, group=group, cplx=cplx):
+            try:
+                if cplx:       # RCCL has no complex type: ship interleaved (re, im) doubles
+                    import torch
+                    _dist().all_gather_into_tensor(recv.view(torch.float64), send.view(torch.float64), group=group)
+                else:
+                    _dist().all_gather_into_tensor(recv, send, group=group)
+                return 0
+            except BaseException:      # must not unwind through the C frame
+                import traceback
+                traceback.print_exc()
+                return 1
+        collective.agree = lambda failed, group=group: _agree_failure(failed, group)
+        return prog.finish((), collective), s['p2']
+
+    def _use_sharded(self, s):
+        """Keep the tables ``s`` of ``_build_sharded`` / ``_build_sharded_factored`` (``None``: there are none) with their counts."""
+        self._sharded = s
+        if s is not None:
+            self._set_counts(s['p1'], s['p2'], s['a01'].bytes if self.factored else 0)
 
     def matvec(self, theta):
         if self.world == 1 and not _forced():
@@ -406,12 +384,9 @@ class ShardedTwoSiteH(TwoSiteH):
                 return self.prepare_svd(self._matvec_sharded_factored(self.combine_theta(theta)))
             return self._matvec_sharded_factored(theta)
         if self._sharded is None or self._sharded['key'] != (theta._struct_key(), theta.dtype):
-            self._sharded = self._build_sharded(theta)
+            self._use_sharded(self._build_sharded(theta))
             if self._sharded is None:
                 return super().matvec(theta)
-            s = self._sharded
-            self.flops_per_matvec = s['p1'].flops + s['p2'].flops
-            self.bytes_per_matvec = s['p1'].bytes_min + s['p2'].bytes_min
         s = self._sharded
         tmp = s['tmp']
         if not s['sp1'].local_empty:
