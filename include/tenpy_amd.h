@@ -181,6 +181,35 @@ int tpa_lanczos_step(int dtype, int64_t n, void *w_dev, const void *v1_dev, cons
 int tpa_project_out(int dtype, int64_t n, const void *basis_dev, int m, int64_t stride, const void *src_dev, void *dst_dev,
                     double *coeff_dev, double *nrm2_out_dev, double *work_dev, void *stream);
 
+/* Many inner products <b| op |x_s> with a small matrix on the physical index in ONE launch pair: the closing values of all started
+ * rows of MPS.correlation_function at one site (reference networks/mps.py:1312-1316: tensordot(op2, C), inner(B.conj(), Cij) -- per
+ * row i -- and the one-site MPS.expectation_value, :591-596), the rows stacked on a stride of x.  A job is one pair of charge blocks:
+ * b block (pre, d_b, post), x block (pre, [stack,] d_x, post) with the stack index anywhere (x_sstride), coeff the (d_b, d_x) sector
+ * block of the operator, out_col the operator.
+ * jobs : int64[n_jobs][12] = {b_off, b_ld, d_b, x_off, x_ld, x_sstride, d_x, pre, post, coeff_off, out_col, 0}
+ *   out[2*(s*n_out + k) + (0|1)] = (re | im) of
+ *      sum_{jobs with out_col == k} sum_{i<pre} sum_{j<post} sum_{o<d_b} sum_{c<d_x}
+ *          conj(b[b_off + i*b_ld + o*post + j]) * coeff[coeff_off + o*d_x + c] * x[x_off + i*x_ld + s*x_sstride + c*post + j]
+ *   for s < n_stack, k < n_out        (im = 0 for F64)
+ * Offsets and strides in elements of dtype; coeff_dev holds elements of dtype.  1 <= max_d <= TPA_MPO_APPLY_MAXD bounds every d_b and
+ * d_x of the call (it selects the register budget of the kernel, the convention of tpa_mpo_apply_batch); of a job that breaks this,
+ * the terms with o >= max_d or c >= max_d are left out (the coefficient rows stay d_x apart).  x_sstride and x_ld are free: the stack
+ * index may be the slowest index of a block (x_sstride = pre * x_ld) or sit between i and c.  max_job_cols = max pre * post over the
+ * jobs sizes the grid.  Every out[0 : 2*n_stack*n_out] is written exactly once (columns without a job, out_col outside [0, n_out) and
+ * jobs with a zero extent: zeros / no contribution); nothing else is written apart from work_dev[0 : tpa_site_inner_work(n_jobs,
+ * n_stack, n_out, max_job_cols)] (doubles).  b and x are only read and may alias.  Two passes, no atomics: per-workgroup partials in
+ * work_dev, then one workgroup per output adds them in a fixed order -- two identical calls give identical bits.
+ * dtype, max_d, n_stack >= 1, n_out >= 1 and out_dev are checked first; then n_jobs <= 0 posts zeros to out and returns 0; n_jobs >
+ * 65535 (one job per blockIdx.y) and a NULL jobs, coeff, b, x or work pointer return TPA_E_BADARG; all argument errors are found
+ * before anything is launched or written.
+ * Traffic: itemsize sum_jobs pre post (n_stack d_x + ceil(n_stack / 8) d_b) bytes: a thread folds conj(b) coeff of its column into
+ * d_x values once per group of 8 stack slots, then streams x.  16-byte loads where b_base and x_base are 16-byte aligned and, for F64,
+ * post and every offset and stride of the job (b_off, b_ld, x_off, x_ld, x_sstride) are even, decided per job; 8-byte loads
+ * otherwise. */
+int64_t tpa_site_inner_work(int n_jobs, int n_stack, int n_out, int64_t max_job_cols);
+int tpa_site_inner_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const void *coeff_dev, int max_d, int n_stack, int n_out,
+                         int64_t max_job_cols, const void *b_base, const void *x_base, double *out_dev, double *work_dev, void *stream);
+
 /* LanczosGroundState.run as ONE host call (krylov_based.py:645-700 `_build_krylov`; the caller keeps the reference's host
  * logic -- tridiagonal eigh :702, `_converged` :713 -- in `cb`).  The matvec is a replayed "program" of cached launches:
  *   ops : HOST int64[n_ops][12] = {kind, cfg, p0, p1, p2, count, a_slot, b_slot, c_slot, max_elems, 0, 0}

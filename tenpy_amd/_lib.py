@@ -50,6 +50,9 @@ _SIGS = {
                                           ctypes.c_double, ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, _vp, ctypes.c_int, _vp,
                                           ctypes.c_int, _vp, _vp]),
     "tpa_project_out": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "tpa_site_inner_work": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
+    "tpa_site_inner_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                            _vp, _vp, _vp, _vp, _vp]),
     "tpa_lanczos_set_collective": (ctypes.c_int, [COLLECTIVE_CALLBACK, _vp]),
     "tpa_krylov_combine": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "tpa_krylov_combine_z": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, _vp, ctypes.c_int, _vp, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),

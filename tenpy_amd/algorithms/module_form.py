@@ -38,7 +38,7 @@ from ..linalg.charges import DipolarChargeInfo
 from . import mps_common as dev_mc
 
 __all__ = ['device_two_site_h', 'device_one_site_h', 'device_zero_site_h', 'device_sum_operator', 'hinted_mixed_svd', 'device_mixer_mix_rho',
-           'device_subspace_expansion']
+           'device_subspace_expansion', 'device_measure']
 
 # Smallest "largest bond sector" for which the device form is used.  Round 3 measurement (module form on the MI355X, Heisenberg
 # L = 100, mixer ramp): with the reference's own class below 64 -- four generic tensordots with transposed copies per matvec,
@@ -61,7 +61,11 @@ stats = {'device': 0, 'reference': 0,      # bonds handled by the device form / 
          # the two boundary sites of every pass); whole passes handed to the reference's method with ONE counted decline
          # (`explicit_plus_hc`, not finite: it refuses them before its loop); declines by reason: `mps_common.zipup_stats['why']`, so
          # zipup_reference - zipup_boundary == declined - zipup_handed_back
-         'zipup_device': 0, 'zipup_reference': 0, 'zipup_boundary': 0, 'zipup_handed_back': 0}
+         'zipup_device': 0, 'zipup_reference': 0, 'zipup_boundary': 0, 'zipup_handed_back': 0,
+         # MPS.correlation_function / one-site MPS.expectation_value: calls (per triangle of a correlation matrix) whose values came
+         # from `networks/measure.py` (the stacked walk, `tpa_site_inner_batch`) / from the reference's statements, the latter each
+         # with a reason in `measure.measure_stats['why']`
+         'measure_device': 0, 'measure_reference': 0}
 
 
 def device_two_site_h(Ref):
@@ -377,6 +381,110 @@ def device_apply_zipup(ref_method, ref_mpo):
     apply_zipup.__doc__ = ref_method.__doc__
     apply_zipup._tpa_wrapped = True
     return apply_zipup
+
+
+def device_measure(ref_mps):
+    """Wraps ``correlation_function`` and ``expectation_value`` of the reference's ``BaseMPSExpectationValue`` (networks/mps.py:680-887,
+    :462-596) IN PLACE.  The reference's own methods run -- ``_correlation_function_args``, the Jordan-Wigner decision, the diagonal,
+    ``_normalize_exp_val`` -- and only the rows they ask ``_corr_up_diag`` for come from ONE stacked walk per triangle
+    (``measure.device_corr_up``); a one-site ``expectation_value`` is one ``tpa_site_inner_batch`` launch per site and one host read.
+    Everything else -- ``MPSEnvironment`` (bra != ket), infinite chains, multi-site operators, operators that need a string on the
+    left, what ``measure.decline_reason`` names -- runs the reference's statements, counted with its reason."""
+    from ..networks import measure
+    Base = ref_mps.BaseMPSExpectationValue
+    ref_corr, ref_exp = Base.correlation_function, Base.expectation_value
+
+    def handed_back(why):
+        stats['measure_reference'] += 1
+        measure._count_why(why)
+
+    def route_reason(self):
+        if not measure.MEASURE:
+            return 'switched_off'
+        if not isinstance(self, ref_mps.MPS):
+            return 'environment'
+        if not self.finite:
+            return 'infinite'
+        return None
+
+    def site_ops(self, op_list, what):
+        """The operators of all sites as device Arrays (``None`` entries stay; the route reads each distinct one once per call); raises
+        ``LookupError`` with a decline reason for what the route does not take."""
+        out = []
+        for k in range(self.L):
+            op, needs_JW = self.get_op(op_list, k)
+            if op is not None:
+                if what != 'corr' and needs_JW:
+                    raise LookupError('needs_JW')
+                if op.rank != 2:
+                    raise LookupError('multi_site')
+            out.append(op)
+        return out
+
+    def correlation_function(self, ops1, ops2, sites1=None, sites2=None, opstr=None, str_on_first=True, hermitian=False, autoJW=True):
+        why = route_reason(self)
+        if why is not None:
+            handed_back(why)
+            return ref_corr(self, ops1, ops2, sites1, sites2, opstr, str_on_first, hermitian, autoJW)
+        _, _, s1, s2, _ = self._correlation_function_args(ops1, ops2, sites1, sites2, opstr)      # (the sites as the reference sorts them)
+        s1, s2 = [int(i) for i in s1], [int(j) for j in s2]
+        served = {}
+        ref_rows = type(self)._corr_up_diag
+
+        def rows(o1, o2, i, j_gtr, ostr, str_first, apply_first):
+            key = bool(apply_first)
+            if key not in served:
+                starts, ends = (s1, s2) if apply_first else (s2, s1)
+                try:
+                    a, b, strs = site_ops(self, o1, 'corr'), site_ops(self, o2, 'corr'), site_ops(self, ostr, 'corr')
+                    strs = None if all(o is None for o in strs) else strs
+                    reason = measure.decline_reason(self, a, b, strs)
+                except LookupError as e:
+                    reason = str(e)
+                if reason is None:
+                    stats['measure_device'] += 1
+                    measure.measure_stats['device'] += 1
+                    served[key] = (starts, ends, measure.device_corr_up(self, a, b, starts, ends, strs, str_first, apply_first))
+                else:
+                    handed_back(reason)
+                    served[key] = None
+            if served[key] is None:
+                return ref_rows(self, o1, o2, i, j_gtr, ostr, str_first, apply_first)
+            starts, ends, M = served[key]
+            x = starts.index(int(i))
+            return [M[x, ends.index(int(j))] for j in j_gtr]
+
+        self._corr_up_diag = rows           # (an instance attribute for the duration of the call)
+        try:
+            return ref_corr(self, ops1, ops2, sites1, sites2, opstr, str_on_first, hermitian, autoJW)
+        finally:
+            del self.__dict__['_corr_up_diag']
+
+    def expectation_value(self, ops, sites=None, axes=None):
+        why = route_reason(self)
+        if why is None:
+            try:
+                op_list, site_list, n, (ax_p, ax_pstar) = self._expectation_value_args(ops, sites, axes)
+                if n != 1:
+                    why = 'multi_site'
+                elif list(ax_p) != ['p'] or list(ax_pstar) != ['p*']:
+                    why = 'p_label'
+                else:
+                    per_site = site_ops(self, op_list, 'exp')
+                    why = measure.decline_reason(self, per_site, per_site)
+            except LookupError as e:
+                why = str(e)
+        if why is not None:
+            handed_back(why)
+            return ref_exp(self, ops, sites, axes)
+        stats['measure_device'] += 1
+        measure.measure_stats['device'] += 1
+        E = measure.device_expectation_value(self, [per_site], [int(i) for i in site_list])[:, 0]
+        return self._normalize_exp_val(E)
+
+    correlation_function.__doc__, expectation_value.__doc__ = ref_corr.__doc__, ref_exp.__doc__
+    correlation_function._tpa_wrapped = expectation_value._tpa_wrapped = True
+    Base.correlation_function, Base.expectation_value = correlation_function, expectation_value
 
 
 def batched_tebd_evolve_step(ref_tebd):

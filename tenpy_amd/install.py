@@ -114,6 +114,12 @@ def use_fused_callers():
       place: the matrix of every interior site is one GEMM over chi and the MPO step on the device (``mps_common.device_zipup_step``,
       ``tpa_mpo_cell_apply_batch`` / ``tpa_mpo_expand_batch``), the boundary sites and declined sites run the reference's statements
       (``module_form.stats['zipup_device']`` / ``['zipup_reference']``, reasons in ``mps_common.zipup_stats['why']``).
+    * ``MPS.correlation_function`` and the one-site case of ``MPS.expectation_value`` (``networks/mps.py:680`` / ``:462``) are wrapped in
+      place (``module_form.device_measure``): the reference's argument handling runs, the rows of a correlation matrix come from one
+      stacked walk over the chain and one ``tpa_site_inner_batch`` launch per closing site (``networks/measure.py``); ``MPSEnvironment``,
+      infinite chains, multi-site operators and the ``term_*`` functions keep the reference's statements
+      (``module_form.stats['measure_device']`` / ``['measure_reference']``, reasons in ``measure.measure_stats['why']``; ``TPA_MEASURE=0``
+      switches the route off).
     * ``TEBDEngine.evolve_step`` (``tebd.py:374``; inherited by ``QRBasedTEBDEngine``) -> the bonds of a half-step decomposed in one
       batched device call (``module_form.batched_tebd_evolve_step``; the per-bond statements stay the reference's).
     * ``LanczosEvolution`` (``linalg/krylov_based.py:718``; constructed at ``tdvp.py:132 _krylov_evolve``) -> the device class: the
@@ -158,6 +164,9 @@ def use_fused_callers():
     import tenpy.networks.mpo as ref_mpo
     if not getattr(ref_mpo.MPO.apply_zipup, '_tpa_wrapped', False):
         ref_mpo.MPO.apply_zipup = module_form.device_apply_zipup(ref_mpo.MPO.apply_zipup, ref_mpo)
+    import tenpy.networks.mps as ref_mps
+    if not getattr(ref_mps.BaseMPSExpectationValue.correlation_function, '_tpa_wrapped', False):
+        module_form.device_measure(ref_mps)
     import tenpy.algorithms.tebd as ref_tebd
     if not getattr(ref_tebd.TEBDEngine.evolve_step, '_tpa_wrapped', False):
         ref_tebd.TEBDEngine.evolve_step = module_form.batched_tebd_evolve_step(ref_tebd)

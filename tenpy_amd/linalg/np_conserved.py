@@ -1656,6 +1656,8 @@ def clear_device_caches():
         _mc.MpoExpandPlan._cache.clear()
         _mc.MpoZipupPlan._cache.clear()
         _mc._skip_table_cache.clear()
+        from ..networks import measure as _ms
+        _ms.clear_caches()
     except ImportError:      # (the linalg package is importable on its own)
         pass
 

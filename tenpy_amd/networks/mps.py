@@ -108,8 +108,18 @@ class MPS:
     def expectation_value(self, op, sites=None):
         """``<psi| op_i |psi>`` for every site in ``sites`` (default: all): ``op`` is a dense (d, d) host matrix [p, p*] (must
         conserve the charges) or a device Array with labels 'p', 'p*' (reference ``MPS.expectation_value`` for one-site
-        operators, mps.py).  One tensordot and one inner product per site on the device."""
+        operators, mps.py).  One tensordot and one inner product per site on the device.
+
+        ``op`` may also be a list (or tuple) of such operators: the result is then a list with one array per operator, from one
+        ``tpa_site_inner_batch`` launch per site for all of them and one host read for the whole call (``networks/measure.py``) --
+        or, where ``measure.decline_reason`` names a reason (counted in ``measure.measure_stats['why']``), from the statements of
+        the one-operator form."""
         sites = range(self.L) if sites is None else sites
+        if isinstance(op, (list, tuple)):
+            from . import measure
+            hosts = {}
+            vals = measure.expectation_values(self, [self._site_ops(o, hosts) for o in op], list(sites), hosts)
+            return [np.real_if_close(vals[:, k]) for k in range(len(op))]
         res = []
         for i in sites:
             th = self.get_B(i, 'Th')
@@ -122,6 +132,65 @@ class MPS:
             res.append(npc.inner(th, C, axes='labels', do_conj=True))
         res = np.array(res)
         return np.real_if_close(res)
+
+    def _site_ops(self, op, hosts=None):
+        """``op`` (dense host matrix or device Array, 'p', 'p*') as one device Array per site; sites sharing a leg share the Array.
+        ``hosts``: the call's table of host copies (``measure.as_site_op``)."""
+        from . import measure
+        made = {}
+        for leg in self.p_legs:
+            if id(leg) not in made:
+                made[id(leg)] = measure.as_site_op(op, leg, hosts)
+        return [made[id(leg)] for leg in self.p_legs]
+
+    def correlation_function(self, op1, op2, sites1=None, sites2=None, opstr=None, str_on_first=True, hermitian=False):
+        """``C[x, y] = <psi| op1_i op2_j |psi>`` for i = sites1[x], j = sites2[y] (default: all sites; both are sorted), a complex
+        matrix unless all imaginary parts vanish (reference ``MPS.correlation_function``, mps.py:680-887).  The operators are dense
+        (d, d) host matrices [p, p*] or device Arrays with the labels 'p', 'p*'; charged ones (Sp, Sm, Cd, C) are fine.  There are no
+        site classes here, hence no ``autoJW``: a Jordan-Wigner string is passed as ``opstr``, which is applied on the sites between
+        i and j and -- with ``str_on_first`` -- multiplied onto the operator of the smaller of the two sites, as in the reference.
+        The diagonal is the expectation value of ``op1 . op2`` (``measure.expectation_values``); ``hermitian=True`` (only for sites1 == sites2) takes the lower
+        triangle as the conjugate of the upper one, ``hermitian=False`` costs a second walk with the operators exchanged.
+        The rows come from one stacked walk over the chain (``measure.corr_up`` / ``device_corr_up``) unless
+        ``measure.decline_reason`` names a reason for the row-by-row statements (``measure.measure_stats['why']``)."""
+        from . import measure
+        sites1 = np.sort(np.arange(self.L) if sites1 is None else np.asarray(sites1, dtype=np.int64).reshape(-1))
+        sites2 = np.sort(np.arange(self.L) if sites2 is None else np.asarray(sites2, dtype=np.int64).reshape(-1))
+        for s in (sites1, sites2):
+            if len(s) and (s[0] < 0 or s[-1] >= self.L):
+                raise ValueError("site index out of range for a finite chain")
+        hosts = {}
+        ops1 = self._site_ops(op1, hosts)
+        ops2 = self._site_ops(op2, hosts)
+        strs = None if opstr is None else self._site_ops(opstr, hosts)
+        if hermitian and not np.array_equal(sites1, sites2):
+            hermitian = False
+        C = np.zeros((len(sites1), len(sites2)), dtype=np.complex128)
+        above = sites2[None, :] > sites1[:, None]
+        up = measure.corr_up(self, ops1, ops2, sites1, sites2, strs, str_on_first, True, hosts=hosts)
+        C[above] = up[above]
+        below = sites1[:, None] > sites2[None, :]
+        if hermitian:
+            C[below] = np.conj(up).T[below]
+        else:
+            low = measure.corr_up(self, ops2, ops1, sites2, sites1, strs, str_on_first, False, hosts=hosts)      # [y, x]: the values with sites1[x] > sites2[y]
+            C[below] = low.T[below]
+        same = sites2[None, :] == sites1[:, None]
+        if np.any(same):
+            diag_sites = sorted(set(int(i) for i in sites1) & set(int(j) for j in sites2))
+            prod = {}           # op1 . op2 once per pair of (shared) site operators; its host copy where both factors have one
+            for i in range(self.L):
+                key = (id(ops1[i]), id(ops2[i]))
+                if key not in prod:
+                    prod[key] = npc.tensordot(ops1[i], ops2[i], axes=['p*', 'p'])
+                    if key[0] in hosts and key[1] in hosts:
+                        hosts[id(prod[key])] = (prod[key], hosts[key[0]][1] @ hosts[key[1]][1])
+            op12 = [prod[(id(ops1[i]), id(ops2[i]))] for i in range(self.L)]
+            on_site = measure.expectation_values(self, [op12], diag_sites, hosts)[:, 0]       # one launch per site, one host read
+            vals = dict(zip(diag_sites, on_site))
+            for x, y in zip(*np.nonzero(same)):
+                C[x, y] = vals[int(sites1[x])]
+        return np.real_if_close(C)
 
     def copy(self):
         """Copy sharing the (immutable) tensors: the engines replace tensors, they never modify them in place."""
