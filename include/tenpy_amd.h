@@ -210,6 +210,46 @@ int64_t tpa_site_inner_work(int n_jobs, int n_stack, int n_out, int64_t max_job_
 int tpa_site_inner_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const void *coeff_dev, int max_d, int n_stack, int n_out,
                          int64_t max_job_cols, const void *b_base, const void *x_base, double *out_dev, double *work_dev, void *stream);
 
+/* Projective sampling of a whole stack of rows at one site: MPS.sample_measurements (reference networks/mps.py:4403-4433) computes,
+ * per sample, rho = tensordot(theta.conj(), theta), reads its diagonal on the host, draws rng.choice(dim, p = diag / sum), takes
+ * theta.take_slice(sigma, 'p'), reads its norm on the host and divides by it.  Here X = V . B_i holds the theta of every sample as a
+ * row of a charge block (rows, d, post): tpa_sample_select_batch turns every row into probabilities and an outcome,
+ * tpa_sample_gather_batch writes the chosen slices, divided by their norms, into the next stack.
+ * segs   : int64[n_segs][8]   = {x_off, x_ld, d, post, sigma0, 0, 0, 0}   one charge block of x; sigma0 = the index on the site's
+ *          physical leg of its first state
+ * groups : int64[n_groups][4] = {seg_first, seg_count, row_first, n_rows}  the rows [row_first, row_first + n_rows) of one sector of
+ *          the stack leg and its segs [seg_first, seg_first + seg_count); these have disjoint [sigma0, sigma0 + d), ascending in sigma0
+ * u      : double[n_rows_total], one uniform number in [0, 1) per row;   out : double[n_rows_total][4] = {sigma, w, total, 0}
+ * For row r of group g, with i = r - row_first:
+ *   p[sigma] = sum_{j < post} |x[x_off + i*x_ld + (sigma - sigma0)*post + j]|^2   for every sigma a seg of g covers (inside [0, dim)),
+ *   p[sigma] = 0 exactly for every other sigma < dim;
+ *   total = p[0] + p[1] + ... + p[dim-1], added sequentially in this order;  cdf_k = (p[0] + ... + p[k]) / total, the same sequential sums;
+ *   sigma = min(#{k : cdf_k <= u[r]}, the last sigma with p > 0);   w = sqrt(p[sigma])
+ * -- numpy's Generator.choice(dim, p = p / total) with its one random() replaced by u[r]: cdf.searchsorted(u, side = 'right'); an
+ * outcome with p = 0 is never chosen, u = 0 included.  total == 0 or not finite: sigma = -1, w = 0 (total as computed).  A row that no
+ * group holds gets {-1, 0, 0, 0}.  Offsets and strides in elements of dtype.  1 <= dim <= TPA_SAMPLE_MAX_DIM.
+ * Written: out[0 : 4*n_rows_total], every entry exactly once; nothing else -- no work area.  x, u and the tables are only read.  The
+ * sums of squares are reduced in a fixed order (lanes of a wavefront by shuffles, the four wavefronts of the row's workgroup through
+ * LDS), no atomics: two identical calls give identical bits.
+ * TPA_E_BADARG, found before anything is launched: dtype, dim outside [1, TPA_SAMPLE_MAX_DIM], n_segs < 0 or n_groups < 0, and (for
+ * n_rows_total > 0) a NULL segs, groups, x, u or out pointer.  n_rows_total <= 0 is a no-op that returns 0.
+ * Traffic: itemsize * sum_segs rows d post bytes, every element of x once, plus 40 bytes per row.  16-byte loads where x_base is 16-byte
+ * aligned and, for F64, post, x_off and x_ld of the seg are even, decided per seg; 8-byte loads otherwise. */
+#define TPA_SAMPLE_MAX_DIM 64
+int tpa_sample_select_batch(int dtype, const int64_t *segs_dev, int n_segs, const int64_t *groups_dev, int n_groups, int dim,
+                            int64_t n_rows_total, const void *x_base, const double *u_dev, double *out_dev, void *stream);
+/* rows : int64[n_rows][4] = {src_off, len, dst_off, out_row}
+ *   dst[dst_off + j] = src[src_off + j] / out[4*out_row + 1]      for j < len
+ * (reference networks/mps.py:4426-4431: theta.take_slice(sigma, 'p') / npc.norm(theta)) -- a true division, component by component
+ * for C128, so the result is bitwise what the w of tpa_sample_select_batch gives; w is read from the device, it is not checked (the
+ * caller has looked at out before it builds the table).  Written: the len elements of every row of the table, nothing else; rows with
+ * len <= 0 write nothing.  src and out are only read; src and dst are different buffers, the destinations are disjoint.
+ * TPA_E_BADARG, found before anything is launched: dtype, and (for n_rows > 0) a NULL pointer or src_base == dst_base.  n_rows <= 0 is
+ * a no-op that returns 0.  Traffic: 2 itemsize sum len bytes.  16-byte loads and stores for the rows whose source and destination
+ * addresses are both 16-byte aligned, 8-byte ones otherwise. */
+int tpa_sample_gather_batch(int dtype, const int64_t *rows_dev, int64_t n_rows, const void *src_base, const double *out_dev,
+                            void *dst_base, void *stream);
+
 /* LanczosGroundState.run as ONE host call (krylov_based.py:645-700 `_build_krylov`; the caller keeps the reference's host
  * logic -- tridiagonal eigh :702, `_converged` :713 -- in `cb`).  The matvec is a replayed "program" of cached launches:
  *   ops : HOST int64[n_ops][12] = {kind, cfg, p0, p1, p2, count, a_slot, b_slot, c_slot, max_elems, 0, 0}

@@ -38,7 +38,7 @@ from ..linalg.charges import DipolarChargeInfo
 from . import mps_common as dev_mc
 
 __all__ = ['device_two_site_h', 'device_one_site_h', 'device_zero_site_h', 'device_sum_operator', 'hinted_mixed_svd', 'device_mixer_mix_rho',
-           'device_subspace_expansion', 'device_measure']
+           'device_subspace_expansion', 'device_measure', 'device_sample']
 
 # Smallest "largest bond sector" for which the device form is used.  Round 3 measurement (module form on the MI355X, Heisenberg
 # L = 100, mixer ramp): with the reference's own class below 64 -- four generic tensordots with transposed copies per matvec,
@@ -65,7 +65,10 @@ stats = {'device': 0, 'reference': 0,      # bonds handled by the device form / 
          # MPS.correlation_function / one-site MPS.expectation_value: calls (per triangle of a correlation matrix) whose values came
          # from `networks/measure.py` (the stacked walk, `tpa_site_inner_batch`) / from the reference's statements, the latter each
          # with a reason in `measure.measure_stats['why']`
-         'measure_device': 0, 'measure_reference': 0}
+         'measure_device': 0, 'measure_reference': 0,
+         # calls of ``MPS.sample_measurements`` served by the batched walk of `networks/sample.py` (`tpa_sample_select_batch` /
+         # `tpa_sample_gather_batch`) / by the reference's own method, the latter each with a reason in `sample.sample_stats['why']`
+         'sample_device': 0, 'sample_reference': 0}
 
 
 def device_two_site_h(Ref):
@@ -485,6 +488,33 @@ def device_measure(ref_mps):
     correlation_function.__doc__, expectation_value.__doc__ = ref_corr.__doc__, ref_exp.__doc__
     correlation_function._tpa_wrapped = expectation_value._tpa_wrapped = True
     Base.correlation_function, Base.expectation_value = correlation_function, expectation_value
+
+
+def device_sample(ref_mps):
+    """Wraps ``MPS.sample_measurements`` of the reference (networks/mps.py:4349-4442) IN PLACE and gives it the extra keyword
+    ``n_samples``: ``None`` returns what the reference returns (a list and a scalar), n returns ``(ndarray (n, n_sites), ndarray (n,))``,
+    outcome for outcome what n consecutive calls with the same generator return.  Calls that ``sample.decline_reason`` takes run the
+    batched walk of ``networks/sample.py`` (three device steps and one host read per site for the whole batch); everything else --
+    infinite and segment boundary conditions, subclasses (``UniformMPS`` comes here through ``super()``), ``first_site`` inside the
+    chain, several physical legs, sites wider than ``TPA_SAMPLE_MAX_DIM``, ``TPA_SAMPLE=0`` and, with ``TPA_SAMPLE_SINGLE=0``,
+    single-sample calls -- runs the reference's own method untouched, n times for a batch, counted with its reason.  ``PurificationMPS`` overrides the method and is not touched."""
+    from ..networks import sample
+    ref_sample = ref_mps.MPS.sample_measurements
+
+    def sample_measurements(self, first_site=0, last_site=None, ops=None, rng=None, norm_tol=1.e-12, complex_amplitude=True, n_samples=None):
+        why = 'not_plain_finite' if type(self) is not ref_mps.MPS else sample.decline_reason(self, first_site, last_site, n_samples)
+        if rng is None:
+            rng = np.random.default_rng()
+        if why is None:
+            stats['sample_device'] += 1
+        else:
+            stats['sample_reference'] += 1
+        return sample.sample_measurements(self, first_site, last_site, ops, rng, norm_tol, complex_amplitude, n_samples, why=why,
+                                          generic=lambda: ref_sample(self, first_site, last_site, ops, rng, norm_tol, complex_amplitude))
+
+    sample_measurements.__doc__ = ref_sample.__doc__
+    sample_measurements._tpa_wrapped = True
+    ref_mps.MPS.sample_measurements = sample_measurements
 
 
 def batched_tebd_evolve_step(ref_tebd):

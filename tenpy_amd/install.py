@@ -120,6 +120,12 @@ def use_fused_callers():
       infinite chains, multi-site operators and the ``term_*`` functions keep the reference's statements
       (``module_form.stats['measure_device']`` / ``['measure_reference']``, reasons in ``measure.measure_stats['why']``; ``TPA_MEASURE=0``
       switches the route off).
+    * ``MPS.sample_measurements`` (``networks/mps.py:4349``) is wrapped in place (``module_form.device_sample``) and takes the extra
+      keyword ``n_samples``: a batch of samples is carried through a finite chain as one stack, per site one GEMM, one
+      ``tpa_sample_select_batch`` and one ``tpa_sample_gather_batch`` launch and one host read (``networks/sample.py``); infinite and
+      segment chains, subclasses and ``first_site > 0`` inside the chain run the reference's own method
+      (``module_form.stats['sample_device']`` / ``['sample_reference']``, reasons in ``sample.sample_stats['why']``; ``TPA_SAMPLE=0``
+      switches the route off, ``TPA_SAMPLE_SINGLE=0`` does so for single-sample calls only; defaults: ``profiles/sample.txt``).
     * ``TEBDEngine.evolve_step`` (``tebd.py:374``; inherited by ``QRBasedTEBDEngine``) -> the bonds of a half-step decomposed in one
       batched device call (``module_form.batched_tebd_evolve_step``; the per-bond statements stay the reference's).
     * ``LanczosEvolution`` (``linalg/krylov_based.py:718``; constructed at ``tdvp.py:132 _krylov_evolve``) -> the device class: the
@@ -167,6 +173,8 @@ def use_fused_callers():
     import tenpy.networks.mps as ref_mps
     if not getattr(ref_mps.BaseMPSExpectationValue.correlation_function, '_tpa_wrapped', False):
         module_form.device_measure(ref_mps)
+    if not getattr(ref_mps.MPS.sample_measurements, '_tpa_wrapped', False):
+        module_form.device_sample(ref_mps)
     import tenpy.algorithms.tebd as ref_tebd
     if not getattr(ref_tebd.TEBDEngine.evolve_step, '_tpa_wrapped', False):
         ref_tebd.TEBDEngine.evolve_step = module_form.batched_tebd_evolve_step(ref_tebd)

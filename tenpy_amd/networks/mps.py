@@ -192,6 +192,24 @@ class MPS:
                 C[x, y] = vals[int(sites1[x])]
         return np.real_if_close(C)
 
+    def sample_measurements(self, first_site=0, last_site=None, ops=None, rng=None, norm_tol=1.e-12, complex_amplitude=True, n_samples=None):
+        """Projective measurements on the sites ``first_site .. last_site`` (default: to the end of the chain), the other sites traced
+        out (reference ``MPS.sample_measurements``, mps.py:4349-4442).  ``ops``: a list of dense Hermitian (d, d) host matrices [p, p*]
+        or device Arrays ('p', 'p*') -- there are no site classes here -- of which ``ops[(i - first_site) % len(ops)]`` is measured at
+        site i and its eigenvalue returned; without ``ops`` the outcome is the index of the local basis state.  ``rng``: a
+        ``numpy.random.Generator`` (default: a new one).  With ``n_samples=None`` the result is the reference's: ``(sigmas, weight)``,
+        a list and a scalar -- ``weight`` the amplitude ``<sigmas|psi>`` with its phase for a whole chain, else the square root of the
+        probability; with ``complex_amplitude=False`` the reference's ``abs(total_weight)**2``, which it takes after every site.  With
+        ``n_samples=n`` it is ``(ndarray (n, n_sites), ndarray (n,))``, outcome for outcome what n consecutive single calls with
+        the same generator return: the uniforms are ``rng.random((n, n_sites))``.
+
+        A batch is carried through the chain as one stack, three device steps and one host read of 32 n bytes per site
+        (``networks/sample.py``: ``device_sample``, ``tpa_sample_select_batch`` / ``tpa_sample_gather_batch``), unless
+        ``sample.decline_reason`` names a reason for the sample-by-sample statements (``sample.sample_stats['why']``): ``first_site``
+        inside the chain, a site wider than 64 states, ``TPA_SAMPLE=0``, and ``TPA_SAMPLE_SINGLE=0`` for a single-sample call."""
+        from . import sample
+        return sample.sample_measurements(self, first_site, last_site, ops, rng, norm_tol, complex_amplitude, n_samples)
+
     def copy(self):
         """Copy sharing the (immutable) tensors: the engines replace tensors, they never modify them in place."""
         res = MPS(self.p_legs, list(self._B), list(self._S), form='B')
