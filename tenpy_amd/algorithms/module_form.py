@@ -38,7 +38,7 @@ from ..linalg.charges import DipolarChargeInfo
 from . import mps_common as dev_mc
 
 __all__ = ['device_two_site_h', 'device_one_site_h', 'device_zero_site_h', 'device_sum_operator', 'hinted_mixed_svd', 'device_mixer_mix_rho',
-           'device_subspace_expansion', 'device_measure', 'device_sample']
+           'device_subspace_expansion', 'device_measure', 'device_sample', 'device_moments']
 
 # Smallest "largest bond sector" for which the device form is used.  Round 3 measurement (module form on the MI355X, Heisenberg
 # L = 100, mixer ramp): with the reference's own class below 64 -- four generic tensordots with transposed copies per matvec,
@@ -68,7 +68,10 @@ stats = {'device': 0, 'reference': 0,      # bonds handled by the device form / 
          'measure_device': 0, 'measure_reference': 0,
          # calls of ``MPS.sample_measurements`` served by the batched walk of `networks/sample.py` (`tpa_sample_select_batch` /
          # `tpa_sample_gather_batch`) / by the reference's own method, the latter each with a reason in `sample.sample_stats['why']`
-         'sample_device': 0, 'sample_reference': 0}
+         'sample_device': 0, 'sample_reference': 0,
+         # calls of ``MPO.expectation_value_finite`` / ``MPO.variance`` served by the walk of `networks/moments.py` / by the reference's
+         # own methods, the latter each with a reason in `moments.moments_stats['why']` (infinite MPOs in ``MPO.expectation_value`` too)
+         'moments_device': 0, 'moments_reference': 0}
 
 
 def device_two_site_h(Ref):
@@ -515,6 +518,46 @@ def device_sample(ref_mps):
     sample_measurements.__doc__ = ref_sample.__doc__
     sample_measurements._tpa_wrapped = True
     ref_mps.MPS.sample_measurements = sample_measurements
+
+
+def device_moments(ref_mpo):
+    """Wraps ``MPO.expectation_value_finite`` and ``MPO.variance`` of the reference (networks/mpo.py:1144-1171, :1296-1342) IN PLACE:
+    calls that ``moments.decline_reason`` does not take run the one walk of ``networks/moments.py`` -- ``variance`` without ``exp_val``
+    takes both moments from it --; everything else (segment chains, ``explicit_plus_hc``, given environment data, MPOs without a plan
+    class, wide MPO bonds, ``TPA_MPO_MOMENTS=0``) runs the reference's own method, counted with its reason.  The argument checks of ``variance`` are the
+    reference's, in its order.  ``MPO.expectation_value`` only gains the count of the infinite MPOs it hands to the reference's
+    transfer-matrix and power methods."""
+    from ..networks import moments
+    ref_finite, ref_var, ref_ev = ref_mpo.MPO.expectation_value_finite, ref_mpo.MPO.variance, ref_mpo.MPO.expectation_value
+
+    def served(val_why):
+        stats['moments_device' if val_why[1] is None else 'moments_reference'] += 1
+        return val_why[0]
+
+    def expectation_value_finite(self, psi, init_env_data={}):
+        return served(moments.expectation_value(psi, self, lambda: ref_finite(self, psi, init_env_data), init_env_data))
+
+    def variance(self, psi, exp_val=None):
+        if self.bc != 'finite':
+            raise ValueError('works only for finite systems')
+        if self.L != psi.L:
+            raise ValueError('expect same L')
+        if psi._p_label != ['p']:
+            raise NotImplementedError('not adjusted for non-standard MPS.')
+        if self.explicit_plus_hc:
+            raise NotImplementedError('not implemented for explicit_plus_hc flag')
+        return served(moments.variance(psi, self, exp_val, lambda: ref_var(self, psi, exp_val)))
+
+    def expectation_value(self, psi, tol=1.e-10, max_range=100, init_env_data={}):
+        if not self.finite:
+            stats['moments_reference'] += 1
+            moments._count_why('infinite')
+        return ref_ev(self, psi, tol, max_range, init_env_data)
+
+    for new, ref in ((expectation_value_finite, ref_finite), (variance, ref_var), (expectation_value, ref_ev)):
+        new.__doc__ = ref.__doc__
+        new._tpa_wrapped = True
+        setattr(ref_mpo.MPO, new.__name__, new)
 
 
 def batched_tebd_evolve_step(ref_tebd):

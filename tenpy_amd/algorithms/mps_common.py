@@ -709,6 +709,205 @@ class MpoEntryApplyPlan(_MpoStepPlan):
                 self.max_cols, 0, 0]
 
 
+def _merged_w_leg(leg1, leg2):
+    """The leg ``(w1, w2)`` of two MPO bond legs with the same ``qconj``: one block per pair of blocks, the first leg's block number the
+    slow one, and inside a block the first leg's position the slow one -- which is how a block of a tensor with the neighbouring legs
+    ``w1, w2`` lies in memory, so that merging them (``_with_w_legs``) moves no data."""
+    from ..linalg.charges import LegCharge
+    assert leg1.qconj == leg2.qconj
+    chinfo = leg1.chinfo
+    s1, s2 = np.asarray(leg1.get_block_sizes(), dtype=np.int64), np.asarray(leg2.get_block_sizes(), dtype=np.int64)
+    slices = np.concatenate([[0], np.cumsum(np.outer(s1, s2).reshape(-1))])
+    q1, q2 = np.asarray(leg1.charges).reshape(len(s1), -1), np.asarray(leg2.charges).reshape(len(s2), -1)
+    charges = chinfo.make_valid((q1[:, None, :] + q2[None, :, :]).reshape(len(s1) * len(s2), -1))
+    return LegCharge.from_qind(chinfo, slices, charges, leg1.qconj)
+
+
+def _merged_w_index(leg1, leg2, merged, i1, i2):
+    """The indices on ``merged = _merged_w_leg(leg1, leg2)`` of the index pairs ``(i1, i2)``."""
+    (b1, p1), (b2, p2) = _leg_block_pos(leg1, i1), _leg_block_pos(leg2, i2)
+    s2 = np.asarray(leg2.get_block_sizes(), dtype=np.int64)
+    return np.asarray(merged.slices, dtype=np.int64)[b1 * leg2.block_number + b2] + p1 * s2[b2] + p2
+
+
+def _array_from_entries(legs, labels, idx, vals, dtype, qtotal):
+    """The Array with the entries ``vals`` at the global indices ``idx`` (int64[n, rank], no index twice) and nothing else stored:
+    only the blocks that hold an entry exist -- nothing of the size of the dense tensor is formed."""
+    where = [_leg_block_pos(leg, idx[:, a]) for a, leg in enumerate(legs)]
+    uq, blk = _rank_rows(np.stack([b for b, _ in where], axis=1))
+    res = npc.Array(legs, dtype, qtotal, labels)
+    if len(idx) == 0:
+        return res
+    shapes = res._block_shapes(uq)
+    sizes = np.prod(shapes, axis=1)
+    offs = np.cumsum(sizes) - sizes
+    pos = np.zeros(len(idx), dtype=np.int64)
+    for a, (_, at) in enumerate(where):
+        pos = pos * shapes[blk, a] + at
+    flat = np.zeros(int(np.sum(sizes)), dtype=dtype)
+    flat[offs[blk] + pos] = vals
+    res._set_blocks(uq, arena=dev.to_device(flat), qdata_sorted=True)
+    return res
+
+
+def _with_w_legs(A, at, legs, labels):
+    """``A`` with the MPO bond leg(s) that start at position ``at`` replaced by ``legs`` -- the two legs ``w1, w2`` by their merged leg
+    (``_merged_w_leg``) or the merged leg by the two -- WITHOUT moving data: the blocks keep their places in the arena, only their
+    numbers change."""
+    n_old = 3 - len(legs)
+    q = A._qdata
+    if n_old == 2:
+        mid = (q[:, at] * A.legs[at + 1].block_number + q[:, at + 1])[:, None]
+    else:
+        mid = np.stack(np.divmod(q[:, at], legs[1].block_number), axis=1)
+    qdata = np.concatenate([q[:, :at], mid, q[:, at + n_old:]], axis=1)
+    res = npc.Array(A.legs[:at] + list(legs) + A.legs[at + n_old:], A.dtype, A.qtotal, A._labels[:at] + list(labels) + A._labels[at + n_old:])
+    order = np.lexsort(qdata.T)
+    res._adopt_blocks(np.ascontiguousarray(qdata[order], dtype=np.intp), np.ascontiguousarray(A._offsets[order]), A._arena, True)
+    return res
+
+
+def _pair_tensors(W):
+    """The host-multiplied tensors of the pair step of ``W`` (legs ``wL, wR, p, p*``), each an MPO tensor ``[wL, wR, p, p*]`` on merged
+    bond legs ``(w1, w2)`` (cached on W like ``_tpa_entries``; the tables of the three plan families are then read from them):
+    ``'prod'``: ``sum_p' W[w2, w2'][p'', p'] W[w1, w1'][p', p]``, the two layers of ``H^2`` in one tensor;
+    ``'low'`` : ``W[w1, w1'] (x) 1[w2]``, layer 1 with the bond of layer 2 as a spectator; ``'up'``: ``1[w1'] (x) W[w2, w2']``, layer 2.
+    All three come from the nonzero entries of W (``_mpo_coo``) -- the product by a sorted join over ``p'``, the way the ``W0 W1``
+    tables are joined over their common bond -- and are stored entry by entry: the cost is the number of entries of the results
+    (``nnz^2 / d`` and ``2 D nnz``), never the ``D^4`` of a dense tensor on the merged legs."""
+    pair = getattr(W, '_tpa_pair', None)
+    if pair is None:
+        labels = ['wL', 'wR', 'p', 'p*']
+        idx, vals = _mpo_coo(W)
+        wl = list(W.get_leg_labels())
+        a, b, s, t = (idx[:, wl.index(l)] for l in labels)
+        wL, wR, p, pc = (W.get_leg(l) for l in labels)
+        # layer 2 entry e2 on layer 1 entry e1: p' = p* of e2 = p of e1
+        o1 = np.argsort(s, kind='stable')
+        lo, hi = np.searchsorted(s[o1], t, side='left'), np.searchsorted(s[o1], t, side='right')
+        e2 = np.repeat(np.arange(len(t)), hi - lo)
+        e1 = o1[np.arange(len(e2)) - np.repeat(np.cumsum(hi - lo) - (hi - lo), hi - lo) + np.repeat(lo, hi - lo)]
+        n, c_in, c_out = len(vals), np.arange(wL.ind_len), np.arange(wR.ind_len)
+        rep_in, rep_out = np.repeat(np.arange(n), len(c_in)), np.repeat(np.arange(n), len(c_out))
+        # (w1, w2, w1', w2', p'', p, value), the legs of every bond pair, total charge in units of W's
+        parts = dict(prod=((a[e1], a[e2], b[e1], b[e2], s[e2], t[e1], vals[e2] * vals[e1]), (wL, wL), (wR, wR), 2),
+                     low=((a[rep_in], np.tile(c_in, n), b[rep_in], np.tile(c_in, n), s[rep_in], t[rep_in], vals[rep_in]),
+                          (wL, wL), (wR, wL.conj()), 1),
+                     up=((np.tile(c_out, n), a[rep_out], np.tile(c_out, n), b[rep_out], s[rep_out], t[rep_out], vals[rep_out]),
+                         (wR.conj(), wL), (wR, wR), 1))
+        pair = {}
+        for name, ((w1, w2, w1o, w2o, po, pi, v), l_in, l_out, n_q) in parts.items():
+            leg_in, leg_out = _merged_w_leg(*l_in), _merged_w_leg(*l_out)
+            at = np.stack([_merged_w_index(*l_in, leg_in, w1, w2), _merged_w_index(*l_out, leg_out, w1o, w2o), po, pi], axis=1)
+            uq, inv = np.unique(at, axis=0, return_inverse=True)         # equal indices are summed in a fixed order
+            tot = np.zeros(len(uq), dtype=np.asarray(v).dtype)
+            np.add.at(tot, inv.reshape(-1), v)
+            pair[name] = _array_from_entries([leg_in, leg_out, p, pc], labels, uq[tot != 0], tot[tot != 0], W.dtype,
+                                             W.chinfo.make_valid(n_q * W.qtotal))
+        W._tpa_pair = pair
+    return pair
+
+
+class MpoPairPlan(_MpoStepPlan):
+    """The MPO step of the second moment (``networks/moments.py``): both layers of ``H^2`` on one site,
+
+        ``Y[vR*, p, wR1, wR2, vR] = sum_{w1, w2, p} C[(w1 -> w1'), (w2 -> w2'); p'', p] X[vR*, wR1, wR2, p, vR]``,
+        ``C = sum_p' W[w2, w2'][p'', p'] W[w1, w1'][p', p]``
+
+    with the physical leg of Y next to ``vR*`` (the GEMM that closes the site needs no transposed copy).  The bond legs ``wR1, wR2`` of X
+    are neighbours, so X is -- without moving data -- a tensor ``[vR*, (w1.w2), p, vR]`` on their merged leg, and the step is the
+    one-site step of the plan family that ``_mpo_plan_class`` selects for the MPO, applied to a host-multiplied tensor of
+    ``_pair_tensors``: no kernel and no entry point of its own.  Two modes:
+
+    * ``'product'``  one launch with the product table ``C``;
+    * ``'two_pass'`` two launches, ``W (x) 1`` (layer 1, ``wR2`` a spectator) and ``1 (x) W`` (layer 2): fewer terms where the MPO bond
+      is wide (about ``2 D nnz`` against ``nnz^2 / d``).
+
+    ``two_pass=None`` takes the mode with fewer terms (``n_terms``; a tie goes to the single launch).  ``steps`` are the plans of the
+    family, ``launches`` their number."""
+    _cache = {}
+    _table = staticmethod(_pair_tensors)
+    X_LABELS = ('vR*', 'wR1', 'wR2', 'p', 'vR')
+    Y_LABELS = ('vR*', 'p', 'wR1', 'wR2', 'vR')
+    MAX_JOBS = 60000            # what the job tables of the three plan families take (one job per block of Y)
+    # (blocks of X) x (terms of a table) per site that `modes_within_reach` accepts: the scalar and the block family match them as one
+    # boolean matrix when a plan is built, 2.3 - 2.8 ns per cell (profiles/mpo_moments.txt: 9.8 s for the first `variance` call of an
+    # L = 100 chain at D = 20, 46 s at D = 32, against 0.7 / 1.6 s of the reference's statements); 10^6 keeps the build of a site at
+    # about 3 ms, what the Heisenberg chain (D = 5: 3 10^4 cells) pays several times over -- D up to about 8 for a spin chain
+    MAX_MATCH = 10**6
+
+    @staticmethod
+    def family(W):
+        """The plan class of the pair step of ``W``, ``None`` where there is no blockwise form (``_mpo_plan_class`` of every tensor of
+        ``_pair_tensors``: the merged legs keep the widths' character, so this is the family of ``W`` itself)."""
+        cls = _mpo_plan_class(W)
+        if cls is None or any(_mpo_plan_class(T) is not cls for T in _pair_tensors(W).values()):
+            return None
+        return cls
+
+    @classmethod
+    def modes_within_reach(cls, W, n_blocks, two_pass=None):
+        """The modes -- of both, or the one ``two_pass`` names -- whose plans can be built for an X of at most ``n_blocks`` blocks
+        within ``MAX_MATCH``, from the entry counts of W alone (nothing is multiplied): the product table has
+        ``sum_p' #(p* = p') #(p = p')`` terms, the two passes ``nnz D`` each.  The entry family joins sorted tables and has no such
+        matrix."""
+        modes = ['product', 'two_pass'] if two_pass is None else ['two_pass' if two_pass else 'product']
+        if _mpo_plan_class(W) is MpoEntryApplyPlan:
+            return modes
+        idx, _ = _mpo_coo(W)
+        wl = list(W.get_leg_labels())
+        d = W.get_leg('p').ind_len
+        n_in, n_out = (np.bincount(idx[:, wl.index(l)], minlength=d) for l in ('p*', 'p'))
+        terms = {'product': int(np.sum(n_in * n_out)), 'two_pass': len(idx) * max(W.get_leg('wL').ind_len, W.get_leg('wR').ind_len)}
+        return [m for m in modes if n_blocks * terms[m] <= cls.MAX_MATCH]
+
+    @staticmethod
+    def _one_step(cls, Xm, T, first):
+        out = ('vR*', 'p', 'wR', 'vR') if first else ('vR*', 'wR', 'p', 'vR')
+        return cls.get(Xm, T, 'wR', 'p', 'wL', 'wR', 'p', 'p*', out)
+
+    def __init__(self, X, W, two_pass=None, W2=None):
+        assert W2 is None and tuple(X.get_leg_labels()) == self.X_LABELS
+        cls, pair = self.family(W), _pair_tensors(W)
+        Xm = _with_w_legs(X, 1, [_merged_w_leg(X.legs[1], X.legs[2])], ['wR'])
+        modes = {}          # (only the mode asked for, or both to compare them; what is worth building is the caller's question: `modes_within_reach`)
+        for m in ['product', 'two_pass'] if two_pass is None else ['two_pass' if two_pass else 'product']:
+            if m == 'product':
+                modes[m] = [self._one_step(cls, Xm, pair['prod'], True)]
+            else:
+                low = self._one_step(cls, Xm, pair['low'], False)
+                modes[m] = [low] if low.empty else [low, self._one_step(cls, low.apply(Xm, launch=False), pair['up'], True)]
+        self.n_terms = {m: sum(0 if s.empty else len(s.terms_host) for s in steps) for m, steps in modes.items()}
+        self.mode = min(modes, key=lambda m: (self.n_terms[m], m))          # (a tie goes to 'product', the single launch)
+        self.steps = modes[self.mode]
+        self.launches = len(self.steps)
+        self.empty = any(s.empty for s in self.steps)
+        self.dtype = np.result_type(X.dtype, W.dtype)
+        self.x_key = X._struct_key()
+        if self.empty:
+            self.qtotal = X.chinfo.make_valid(X.qtotal + 2 * W.qtotal)
+            wR = W.get_leg('wR')
+            self.legs, self.labels = [X.legs[0], W.get_leg('p'), wR, wR, X.legs[4]], list(self.Y_LABELS)
+            return
+        Ym = self.steps[-1].apply(Xm, launch=False)             # (block structure only)
+        wR = W.get_leg('wR')
+        Y = _with_w_legs(Ym, 2, [wR, wR], ['wR1', 'wR2'])
+        self.legs, self.labels, self.qtotal = Y.legs, list(Y.get_leg_labels()), Y.qtotal
+        self.qdata, self.offsets, self.total = Y._qdata, Y._offsets, self.steps[-1].total
+        self.bytes = sum(s.bytes for s in self.steps)
+
+    def apply(self, X, launch=True):
+        """Y as a new Array (the plans of ``steps`` read nothing of X but its arena)."""
+        res = npc.Array(self.legs, self.dtype, self.qtotal, self.labels)
+        if self.empty:
+            return res
+        T = X
+        for step in self.steps:
+            T = step.apply(T, launch=launch)
+        res._adopt_blocks(self.qdata, self.offsets, T._arena, True)
+        return res
+
+
 class ExpandJobLimit(ValueError):
     """The expanded matrix has more cells than one ``tpa_mpo_expand_batch`` launch takes jobs."""
 

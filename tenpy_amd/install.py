@@ -126,6 +126,12 @@ def use_fused_callers():
       segment chains, subclasses and ``first_site > 0`` inside the chain run the reference's own method
       (``module_form.stats['sample_device']`` / ``['sample_reference']``, reasons in ``sample.sample_stats['why']``; ``TPA_SAMPLE=0``
       switches the route off, ``TPA_SAMPLE_SINGLE=0`` does so for single-sample calls only; defaults: ``profiles/sample.txt``).
+    * ``MPO.expectation_value_finite`` and ``MPO.variance`` (``networks/mpo.py:1144`` / ``:1296``) are wrapped in place
+      (``module_form.device_moments``): ``<H>`` and ``<H^2>`` of a finite chain come from one left-to-right walk -- per site and row
+      set two grouped GEMMs and one launch of the MPO-step plan of the MPO, ``variance`` without ``exp_val`` takes both moments from
+      the same walk (``networks/moments.py``); segment chains, ``explicit_plus_hc``, given environment data, MPOs without a plan class
+      and MPO bonds wider than about 8 run the reference's own method (``module_form.stats['moments_device']`` / ``['moments_reference']``, reasons in
+      ``moments.moments_stats['why']``; ``TPA_MPO_MOMENTS=0`` switches the route off; default: ``profiles/mpo_moments.txt``).
     * ``TEBDEngine.evolve_step`` (``tebd.py:374``; inherited by ``QRBasedTEBDEngine``) -> the bonds of a half-step decomposed in one
       batched device call (``module_form.batched_tebd_evolve_step``; the per-bond statements stay the reference's).
     * ``LanczosEvolution`` (``linalg/krylov_based.py:718``; constructed at ``tdvp.py:132 _krylov_evolve``) -> the device class: the
@@ -170,6 +176,8 @@ def use_fused_callers():
     import tenpy.networks.mpo as ref_mpo
     if not getattr(ref_mpo.MPO.apply_zipup, '_tpa_wrapped', False):
         ref_mpo.MPO.apply_zipup = module_form.device_apply_zipup(ref_mpo.MPO.apply_zipup, ref_mpo)
+    if not getattr(ref_mpo.MPO.variance, '_tpa_wrapped', False):
+        module_form.device_moments(ref_mpo)
     import tenpy.networks.mps as ref_mps
     if not getattr(ref_mps.BaseMPSExpectationValue.correlation_function, '_tpa_wrapped', False):
         module_form.device_measure(ref_mps)

@@ -1655,6 +1655,7 @@ def clear_device_caches():
         _mc.MpoEntryApplyPlan._cache.clear()
         _mc.MpoExpandPlan._cache.clear()
         _mc.MpoZipupPlan._cache.clear()
+        _mc.MpoPairPlan._cache.clear()
         _mc._skip_table_cache.clear()
         from ..networks import measure as _ms
         _ms.clear_caches()

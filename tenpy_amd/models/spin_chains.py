@@ -11,7 +11,7 @@ import numpy as np
 from ..linalg.charges import ChargeInfo, LegCharge
 from ..networks.mpo import mpo_from_dense
 
-__all__ = ['xxz_chain_mpo', 'tfi_chain_mpo', 'spin_half_leg']
+__all__ = ['xxz_chain_mpo', 'tfi_chain_mpo', 'long_range_xxz_mpo', 'spin_half_leg']
 
 
 def spin_half_leg(conserve='Sz'):
@@ -74,3 +74,20 @@ def tfi_chain_mpo(L, J=1., g=1., conserve=None):
     H = mpo_from_dense(Ws, [p] * L, chinfo)
     H.IdL, H.IdR = 0, -1
     return H
+
+
+def long_range_xxz_mpo(L, k):
+    """``sum_{i<j} sum_n c_n lam_n^(j-i-1) (Sz_i Sz_j + (Sp_i Sm_j + h.c.) / 2)`` with k exponentials: MPO bond dimension 3 k + 2
+    (a chain with a wide MPO bond for tests and measurements of the MPO-step plans)."""
+    chinfo, p = spin_half_leg('Sz')
+    Sz, Sp, Id = np.diag([0.5, -0.5]), np.array([[0., 1.], [0., 0.]]), np.eye(2)
+    ops = [(Sz, Sz), (Sp, 0.5 * Sp.T), (Sp.T, 0.5 * Sp)]
+    D = 3 * k + 2
+    W = np.zeros((D, D, 2, 2))
+    W[0, 0] = W[-1, -1] = Id
+    for n in range(k):
+        for m, (a, b) in enumerate(ops):
+            j = 1 + 3 * n + m
+            W[0, j], W[j, j], W[j, -1] = a, 0.3 * (n + 1) / k * Id, (1. + 0.1 * n) * b
+    Ws = [W[0:1] if i == 0 else (W[:, -1:] if i == L - 1 else W) for i in range(L)]
+    return mpo_from_dense(Ws, [p] * L, chinfo)

@@ -42,6 +42,31 @@ class MPO:
         Id = self.IdR[i + 1] if isinstance(self.IdR, (list, tuple)) else self.IdR
         return Id % self._W[i].get_leg('wR').ind_len
 
+    def expectation_value(self, psi, tol=1.e-10, max_range=100, init_env_data={}):
+        """``<psi|self|psi>`` of a finite chain, ignoring ``psi.norm`` (reference mpo.py:1111-1171; ``tol`` and ``max_range`` concern
+        infinite chains only).  One walk on the device (``networks/moments.py``); where ``moments.decline_reason`` names a reason
+        (counted in ``moments.moments_stats['why']``), the reference's statements: ``MPOEnvironment.full_contraction``."""
+        from . import moments
+        return moments.expectation_value(psi, self, lambda: moments.expectation_value_generic(psi, self), init_env_data)[0]
+
+    def variance(self, psi, exp_val=None):
+        """``<psi|self^2|psi> - <psi|self|psi>^2`` of a finite chain, ignoring ``psi.norm`` (reference mpo.py:1296-1342).  ``exp_val``:
+        ``<psi|self|psi>`` if known (0 gives ``<psi|self^2|psi>`` alone); ``None``: both moments come from the same walk
+        (``networks/moments.py``).  A declined call runs the reference's statements."""
+        from . import moments
+        if self.bc != 'finite':
+            raise ValueError("works only for finite systems")
+        if self.L != psi.L:
+            raise ValueError("expect same L")
+        if getattr(psi, '_p_label', ['p']) != ['p']:
+            raise NotImplementedError("not adjusted for non-standard MPS.")
+        if self.explicit_plus_hc:
+            raise NotImplementedError("not implemented for explicit_plus_hc flag")
+
+        def generic():
+            return moments.variance_generic(psi, self, self.expectation_value(psi) if exp_val is None else exp_val)
+        return moments.variance(psi, self, exp_val, generic)[0]
+
     def apply(self, psi, options):
         """Apply the MPO to ``psi`` in place and compress it (reference mpo.py:1562-1609): ``compression_method='zip_up'`` is the one
         method served -- ``apply_zipup``, then ``psi.compress_svd(trunc_params)``.  Returns the summed truncation error."""
