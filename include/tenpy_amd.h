@@ -210,6 +210,38 @@ int64_t tpa_site_inner_work(int n_jobs, int n_stack, int n_out, int64_t max_job_
 int tpa_site_inner_batch(int dtype, const int64_t *jobs_dev, int n_jobs, const void *coeff_dev, int max_d, int n_stack, int n_out,
                          int64_t max_job_cols, const void *b_base, const void *x_base, double *out_dev, double *work_dev, void *stream);
 
+/* The closing step of a reduced density matrix with the physical index pair left open, for a whole stack of rows in ONE launch pair:
+ * per pair (i, j) MPS.mutinf_two_site closes rho . B_j with tensordot(rho, B.conj(), [['vR*', 'vR'], ['vL*', 'vR*']]) (reference
+ * networks/mps.py:4218-4232), a product that is d^2 rows tall, and reads the result on the host; the one-site density matrix of
+ * get_rho_segment (:4004) is the same contraction with x = b = theta_i and n_stack = 1, out[p', p] = rho_i[p, p'].  A job is one pair
+ * of charge blocks with equal row and column sectors: b block (pre, d_b, post), x block (pre, [stack,] d_x, post) with the stack index
+ * anywhere (x_sstride), the conventions of tpa_site_inner_batch; its d_b x d_x tile lies at (out_off, out_ld) inside the out_size
+ * entries of one slot (for a physical leg of d states: out_size = d * d, out_ld = d, out_off = first o * d + first c of the sectors).
+ * jobs : int64[n_jobs][12] = {b_off, b_ld, d_b, x_off, x_ld, x_sstride, d_x, pre, post, out_off, out_ld, 0}
+ *   out[2*(s*out_size + e) + (0|1)] = (re | im) of
+ *      sum_{jobs, o<d_b, c<d_x with out_off + o*out_ld + c == e} sum_{i<pre} sum_{j<post}
+ *          conj(b[b_off + i*b_ld + o*post + j]) * x[x_off + i*x_ld + s*x_sstride + c*post + j]
+ *   for s < n_stack, e < out_size        (im = 0 for F64)
+ * Offsets and strides in elements of dtype.  1 <= max_d <= TPA_SITE_RHO_MAXD bounds every d_b and d_x of the call (it selects the
+ * register budget: D = 1, 2 or 4 and 8, 4 or 2 stack slots per pass over b); of a job that breaks this, the terms with o >= max_d or
+ * c >= max_d are left out.  Wider sectors are not served.  Several jobs may write one tile; tile entries with out_off + o*out_ld + c
+ * outside [0, out_size), or with o*d_x + c >= min(16, out_size), contribute nothing.  max_job_cols = max pre * post over the jobs
+ * sizes the grid.  Every out[0 : 2*n_stack*out_size] is written exactly once (entries that no job covers, and jobs with a zero
+ * extent: exact zeros / no contribution); nothing else is written apart from work_dev[0 : tpa_site_rho_work(n_jobs, n_stack,
+ * out_size, max_job_cols)] (doubles).  b and x are only read and may alias.  Two passes, no atomics: per-workgroup partials in
+ * work_dev, then one workgroup per output entry gathers and adds them in a fixed order -- two identical calls give identical bits.
+ * (The gather costs n_stack * out_size * n_jobs * grid tile tests: cheap for tens of jobs, not for tens of thousands under a wide stack.)
+ * dtype, max_d, n_stack >= 1, out_size >= 1, n_stack * out_size < 2^31 and out_dev are checked first; then n_jobs <= 0 posts zeros to
+ * out and returns 0; n_jobs > 65535 (one job per blockIdx.y) and a NULL jobs, b, x or work pointer return TPA_E_BADARG; all argument
+ * errors are found before anything is launched or written.
+ * Traffic: itemsize sum_jobs pre post (n_stack d_x + ceil(n_stack / S) d_b) bytes, S = 8, 4, 2 for D = 1, 2, 4.  16-byte loads where
+ * b_base and x_base are 16-byte aligned and, for F64, post and every offset and stride of the job (b_off, b_ld, x_off, x_ld,
+ * x_sstride) are even, decided per job; 8-byte loads otherwise. */
+#define TPA_SITE_RHO_MAXD 4
+int64_t tpa_site_rho_work(int n_jobs, int n_stack, int out_size, int64_t max_job_cols);
+int tpa_site_rho_batch(int dtype, const int64_t *jobs_dev, int n_jobs, int max_d, int n_stack, int out_size, int64_t max_job_cols,
+                       const void *b_base, const void *x_base, double *out_dev, double *work_dev, void *stream);
+
 /* Projective sampling of a whole stack of rows at one site: MPS.sample_measurements (reference networks/mps.py:4403-4433) computes,
  * per sample, rho = tensordot(theta.conj(), theta), reads its diagonal on the host, draws rng.choice(dim, p = diag / sum), takes
  * theta.take_slice(sigma, 'p'), reads its norm on the host and divides by it.  Here X = V . B_i holds the theta of every sample as a

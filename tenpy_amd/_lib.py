@@ -18,6 +18,7 @@ PROJECT_MAX = 64                              # TPA_PROJECT_MAX
 PROJECT_WORK = 2 * 1024 * (PROJECT_MAX + 1)   # TPA_PROJECT_WORK (doubles)
 MPO_APPLY_MAXD = 16                           # TPA_MPO_APPLY_MAXD
 MPO_CELL_MAXROWS = 32                         # TPA_MPO_CELL_MAXROWS
+SITE_RHO_MAXD = 4                             # TPA_SITE_RHO_MAXD
 SAMPLE_MAX_DIM = 64                           # TPA_SAMPLE_MAX_DIM
 
 _lib = None
@@ -54,6 +55,9 @@ _SIGS = {
     "tpa_site_inner_work": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
     "tpa_site_inner_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                             _vp, _vp, _vp, _vp, _vp]),
+    "tpa_site_rho_work": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
+    "tpa_site_rho_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                          _vp, _vp, _vp, _vp, _vp]),
     "tpa_sample_select_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     "tpa_sample_gather_batch": (ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     "tpa_lanczos_set_collective": (ctypes.c_int, [COLLECTIVE_CALLBACK, _vp]),

@@ -38,7 +38,7 @@ from ..linalg.charges import DipolarChargeInfo
 from . import mps_common as dev_mc
 
 __all__ = ['device_two_site_h', 'device_one_site_h', 'device_zero_site_h', 'device_sum_operator', 'hinted_mixed_svd', 'device_mixer_mix_rho',
-           'device_subspace_expansion', 'device_measure', 'device_sample', 'device_moments']
+           'device_subspace_expansion', 'device_measure', 'device_mutinf', 'device_sample', 'device_moments']
 
 # Smallest "largest bond sector" for which the device form is used.  Round 3 measurement (module form on the MI355X, Heisenberg
 # L = 100, mixer ramp): with the reference's own class below 64 -- four generic tensordots with transposed copies per matvec,
@@ -66,6 +66,9 @@ stats = {'device': 0, 'reference': 0,      # bonds handled by the device form / 
          # from `networks/measure.py` (the stacked walk, `tpa_site_inner_batch`) / from the reference's statements, the latter each
          # with a reason in `measure.measure_stats['why']`
          'measure_device': 0, 'measure_reference': 0,
+         # calls of ``MPS.mutinf_two_site`` served by the stacked walk of `networks/rho.py` (`tpa_site_rho_batch`) / by the reference's
+         # own method, the latter each with a reason in `rho.rho_stats['why']`
+         'mutinf_device': 0, 'mutinf_reference': 0,
          # calls of ``MPS.sample_measurements`` served by the batched walk of `networks/sample.py` (`tpa_sample_select_batch` /
          # `tpa_sample_gather_batch`) / by the reference's own method, the latter each with a reason in `sample.sample_stats['why']`
          'sample_device': 0, 'sample_reference': 0,
@@ -491,6 +494,29 @@ def device_measure(ref_mps):
     correlation_function.__doc__, expectation_value.__doc__ = ref_corr.__doc__, ref_exp.__doc__
     correlation_function._tpa_wrapped = expectation_value._tpa_wrapped = True
     Base.correlation_function, Base.expectation_value = correlation_function, expectation_value
+
+
+def device_mutinf(ref_mps):
+    """Wraps ``MPS.mutinf_two_site`` of the reference (networks/mps.py:4180-4233) IN PLACE.  Calls that ``rho.decline_reason`` takes get
+    the two-site density matrices of all pairs from the stacked walk of ``networks/rho.py`` (``device_two_site_rho``: per site and
+    charge difference one GEMM pair and one ``tpa_site_rho_batch`` launch, one device-to-host copy per walk) and the entropies from
+    host eigenvalues per charge block; everything else -- infinite and segment boundary conditions, subclasses, several physical
+    legs, physical sectors wider than 4, ``TPA_MUTINF=0`` -- runs the reference's own method untouched, counted with its reason.
+    ``PurificationMPS`` and ``UniformMPS`` override the method and are not touched."""
+    from ..networks import rho
+    ref_mutinf = ref_mps.MPS.mutinf_two_site
+
+    def mutinf_two_site(self, max_range=None, n=1):
+        why = rho.decline_reason(self, plain=ref_mps.MPS)
+        if why is None:
+            stats['mutinf_device'] += 1
+        else:
+            stats['mutinf_reference'] += 1
+        return rho.mutinf_two_site(self, max_range, n, why=why, generic=lambda: ref_mutinf(self, max_range, n))
+
+    mutinf_two_site.__doc__ = ref_mutinf.__doc__
+    mutinf_two_site._tpa_wrapped = True
+    ref_mps.MPS.mutinf_two_site = mutinf_two_site
 
 
 def device_sample(ref_mps):

@@ -126,6 +126,13 @@ def use_fused_callers():
       segment chains, subclasses and ``first_site > 0`` inside the chain run the reference's own method
       (``module_form.stats['sample_device']`` / ``['sample_reference']``, reasons in ``sample.sample_stats['why']``; ``TPA_SAMPLE=0``
       switches the route off, ``TPA_SAMPLE_SINGLE=0`` does so for single-sample calls only; defaults: ``profiles/sample.txt``).
+    * ``MPS.mutinf_two_site`` (``networks/mps.py:4180``) is wrapped in place (``module_form.device_mutinf``): the two-site density
+      matrices of all pairs come from one stacked walk -- per site and charge difference one GEMM pair and one ``tpa_site_rho_batch``
+      launch that closes every open row with the physical index pair left open, one device-to-host copy per walk -- and the entropies
+      from host eigenvalues per charge block (``networks/rho.py``); infinite and segment chains, subclasses (``PurificationMPS`` and
+      ``UniformMPS`` have methods of their own and are not touched), several physical legs and physical sectors wider than 4 run the
+      reference's own method (``module_form.stats['mutinf_device']`` / ``['mutinf_reference']``, reasons in
+      ``rho.rho_stats['why']``; ``TPA_MUTINF=0`` switches the route off; default: ``profiles/mutinf.txt``).
     * ``MPO.expectation_value_finite`` and ``MPO.variance`` (``networks/mpo.py:1144`` / ``:1296``) are wrapped in place
       (``module_form.device_moments``): ``<H>`` and ``<H^2>`` of a finite chain come from one left-to-right walk -- per site and row
       set two grouped GEMMs and one launch of the MPO-step plan of the MPO, ``variance`` without ``exp_val`` takes both moments from
@@ -181,6 +188,8 @@ def use_fused_callers():
     import tenpy.networks.mps as ref_mps
     if not getattr(ref_mps.BaseMPSExpectationValue.correlation_function, '_tpa_wrapped', False):
         module_form.device_measure(ref_mps)
+    if not getattr(ref_mps.MPS.mutinf_two_site, '_tpa_wrapped', False):
+        module_form.device_mutinf(ref_mps)
     if not getattr(ref_mps.MPS.sample_measurements, '_tpa_wrapped', False):
         module_form.device_sample(ref_mps)
     import tenpy.algorithms.tebd as ref_tebd

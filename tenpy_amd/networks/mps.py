@@ -210,6 +210,41 @@ class MPS:
         from . import sample
         return sample.sample_measurements(self, first_site, last_site, ops, rng, norm_tol, complex_amplitude, n_samples)
 
+    def mutinf_two_site(self, max_range=None, n=1):
+        """``(coords, mutinf)``: the two-site mutual information ``I(i:j) = S(i) + S(j) - S(i, j)`` for all pairs with
+        ``0 < j - i <= max_range`` (default: all), ``coords`` in the order ``for i: for j`` and ``n`` the entropy (1: von Neumann,
+        else Renyi, ``numpy.inf`` included) -- reference ``MPS.mutinf_two_site``, mps.py:4180-4233.  The density matrices come from
+        one stacked walk over the chain (``networks/rho.py``: ``device_two_site_rho``, ``tpa_site_rho_batch``) and the entropies from
+        host eigenvalues per charge block, unless ``rho.decline_reason`` names a reason for the pair-by-pair statements
+        (``rho.rho_stats['why']``): a physical sector wider than 4 states, ``TPA_MUTINF=0``."""
+        from . import rho
+        return rho.mutinf_two_site(self, max_range, n)
+
+    def two_site_rho(self, max_range=None):
+        """``(coords, rhos)``: the reduced density matrices of all pairs of sites with ``0 < j - i <= max_range`` as host arrays
+        ``[p0, p1, p0*, p1*]`` (the reference's ``get_rho_segment([i, j])``, mps.py:3979-4023), ``coords`` as in
+        ``mutinf_two_site``; from the stacked walk of ``networks/rho.py`` or, with a counted reason, pair by pair."""
+        from . import rho
+        why = rho.decline_reason(self)
+        if why is None:
+            rho.rho_stats['device'] += 1
+            return rho.device_two_site_rho(self, max_range)
+        rho.rho_stats['generic'] += 1
+        rho._count_why(why)
+        return rho.two_site_rho_generic(self, max_range)
+
+    def one_site_rho(self):
+        """The one-site density matrices ``[p0, p0*]`` of all sites as host arrays: one ``tpa_site_rho_batch`` launch per site and one
+        host read for all of them (``rho.device_one_site_rho``) or, with a counted reason, site by site."""
+        from . import rho
+        why = rho.decline_reason(self)
+        if why is None:
+            rho.rho_stats['device'] += 1
+            return rho.device_one_site_rho(self)
+        rho.rho_stats['generic'] += 1
+        rho._count_why(why)
+        return rho.one_site_rho_generic(self)
+
     def copy(self):
         """Copy sharing the (immutable) tensors: the engines replace tensors, they never modify them in place."""
         res = MPS(self.p_legs, list(self._B), list(self._S), form='B')
